@@ -7,7 +7,21 @@ synthetic user×item incidence H, i.e. four hgd_spmm hops: CSC (into items) + CS
 forward, the same pair backward. Unit of work = one nonzero of H.
 
     python bench.py [--gpus N --steps K --warmup W --workload synthetic|zipf|ml1m|yelp|amazon
-                     --dim 64|256 --scaling strong|weak]
+                     --dim 64|256 --scaling strong|weak --full --dump-outputs DIR]
+
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline figure needs: it
+builds the graph and the tables, warms up, times the K steps (``ms_per_step`` = the timed
+region's wall time / K), writes the last timed step's outputs if ``--dump-outputs DIR`` is given,
+and prints the result line. Everything below that takes runs of its own at N = 1 — the rocprofv3
+PMC passes (``roofline.traffic``), the stream-copy peak (``roofline.measured_copy_*``), the CPU
+reference with its ``parity`` gate and the ``cpu_baseline`` — runs only with ``--full`` (an
+explicit ``--pmc on`` still collects the counters without it).
+
+``--dump-outputs DIR`` writes what the last timed step returned, ``DIR/Y.npy`` and ``DIR/dX.npy``
+(float32; ``_rank<r>`` is appended to the names at N > 1): all rows, or, above the size budget, a
+fixed sample of rows (numpy generator seed 0, ascending) — the same rows in every run. Graph,
+X and dY come from seeded generators, so two builds run with the same arguments can be compared
+output for output.
 
 N > 1 runs one process per GPU (RCCL over xGMI). Launched without WORLD_SIZE in the environment,
 ``--gpus N`` starts the N ranks itself (a child ``torch.distributed.run``, before this process
@@ -21,7 +35,7 @@ touches the GPU) and exits with its status; under a launcher WORLD_SIZE must equ
 
 Rank 0 prints ONE JSON line. ``roofline`` prices the dominant kernel (hgd_spmm) from HIP events
 recorded around every hop launch on its stream during the timed steps, with SURVEY.md §8d's
-algorithmic bytes. At N = 1 the reference's own library calls (torch.sparse.mm + autograd on CPU,
+algorithmic bytes. At N = 1 with ``--full`` the reference's own library calls (torch.sparse.mm + autograd on CPU,
 oracle/ref_cpu.py) run once on the FULL graph and tables of the GPU run (copied to the host):
 ``parity`` compares one more GPU step with them row by row (the 1e-5 row bound; the script exits
 non-zero if it fails), and ``cpu_baseline`` times the same calls on a bounded prefix sample of
@@ -90,10 +104,19 @@ def parse(argv=None):
     ap.add_argument("--cpu-sample-frac", type=float, default=0.1,
                     help="share of the users (a prefix of the row-sorted graph) the CPU "
                          "baseline's timed runs cover; the parity gate always runs the full graph")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also everything that takes runs of its own beside the timed "
+                         "steps: the rocprofv3 PMC passes, the stream-copy peak, the CPU "
+                         "reference with its parity gate and the cpu_baseline (off by default: "
+                         "a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's Y and dX (float32; "
+                         "above the size budget a fixed seeded sample of rows) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU reference: no cpu_baseline and no parity gate")
+                    help="with --full, skip the CPU reference: no cpu_baseline and no parity gate")
     ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"],
-                    help="measure HBM traffic with rocprofv3 PMC passes in a child process")
+                    help="measure HBM traffic with rocprofv3 PMC passes in a child process "
+                         "(auto: with --full at N = 1 on the synthetic and zipf workloads)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--graph", default="off", choices=["on", "off"],
                     help="replay the fwd+bwd step as one captured hipGraph (measured: no gain "
@@ -348,6 +371,41 @@ def copy_peak_gbps(device, n_bytes=1 << 30, reps=10):
         rates[name] = round(2.0 * n_bytes / (statistics.median(ts) * 1e-3) / 1e9, 1)
     del a, b
     return max(rates.values()), rates
+
+
+DUMP_BUDGET_BYTES = 48 * 10**6  # --dump-outputs: all files of all ranks together
+DUMP_SEED = 0
+
+
+def dump_outputs(path, outputs, rank=0, world=1):
+    """--dump-outputs: every [n, d] tensor of ``outputs`` (name → tensor, the last timed step's
+    results) as ``path/<name>.npy`` in float32 (``<name>_rank<r>.npy`` at N > 1). A tensor whose
+    share of DUMP_BUDGET_BYTES holds fewer than n rows is written as a sample of its rows: k of
+    n drawn without replacement by numpy's default_rng(DUMP_SEED), ascending, so the same rows
+    in every run and the same rows for tensors of the same shape. Returns the record for the
+    result line."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (max(1, world) * max(1, len(outputs)))
+    suffix = "" if world == 1 else f"_rank{rank}"
+    picked = {}
+    files = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        n = int(t.shape[0])
+        k = min(n, share // max(1, 4 * (t.numel() // max(1, n))))
+        if k < n:
+            if (n, k) not in picked:
+                rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+                picked[(n, k)] = torch.from_numpy(rows).to(t.device)
+            t = t.index_select(0, picked[(n, k)])
+        arr = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), arr)
+        files[f"{name}{suffix}.npy"] = {"shape": list(arr.shape), "rows_of": n,
+                                        "sampled": k < n}
+    return {"dir": path, "what": "the last timed step's outputs", "dtype": "float32",
+            "sample_seed": DUMP_SEED, "files": files}
 
 
 def choose_transport(sh, eager_step, device, phase, n=3):
@@ -610,7 +668,7 @@ def main():
 
     pmc = None
     pmc_note = None
-    want_pmc = (args.pmc == "on" or (args.pmc == "auto" and world == 1
+    want_pmc = (args.pmc == "on" or (args.pmc == "auto" and args.full and world == 1
                                      and args.workload in ("synthetic", "zipf")))
     if want_pmc and not args.pmc_child:
         # child profiler processes run BEFORE this process touches the GPU
@@ -669,7 +727,8 @@ def main():
         inc = Incidence.from_coo(idx, None, (U, I), device=device, validate=False,
                                  rows_sorted=True)
         sh = ShardedIncidence(inc, **shard_kw)
-    want_cpu = not args.no_cpu_baseline and world == 1 and not args.pmc_child
+    want_cpu = (args.full and not args.no_cpu_baseline and world == 1
+                and not args.pmc_child)
     idx_host = idx.cpu() if want_cpu else None  # the CPU baseline runs on the same graph
     if not keep_global:
         del idx
@@ -719,6 +778,9 @@ def main():
     # the first timed step's (Y, dX) are kept for the checks (an eager step's outputs; a graph
     # replay overwrites its static outputs)
     keep_first = (args.check or want_cpu) and not use_graph and not args.pmc_child
+    # --dump-outputs: the last timed step's (Y, dX), held (no copy) until they are written
+    want_dump = args.dump_outputs is not None and not args.pmc_child
+    last_out = [None]
     prev = None
     for k in range(args.warmup):
         # each warm-up step's outputs live until the next one's exist, so the allocator caches
@@ -759,15 +821,20 @@ def main():
             dist.barrier()
         t0 = time.perf_counter()
         try:
+            last_out[0] = None
             if use_graph:
                 for _ in range(args.steps):
-                    step()
+                    out_k = step()
+                if want_dump and args.steps > 0:
+                    last_out[0] = (out_k[0].detach(), out_k[1])  # the replay's static outputs
             else:
                 with timer, xtimer:
                     for k in range(args.steps):
                         out_k = step()
                         if k == 0 and keep_first:
                             first = (out_k[0].detach(), out_k[1])
+                        if want_dump and k == args.steps - 1:
+                            last_out[0] = (out_k[0].detach(), out_k[1])
                         del out_k
         except Exception as e:  # noqa: BLE001 — a bounded p2p wait; agreed on below
             if sh.transport != "p2p":
@@ -846,6 +913,11 @@ def main():
              first) = timed_and_checked()
             if failure is not None:
                 raise RuntimeError(f"RCCL timed steps failed: {failure}")
+    dumped = None
+    if want_dump and last_out[0] is not None:
+        dumped = dump_outputs(args.dump_outputs, {"Y": last_out[0][0], "dX": last_out[0][1]},
+                              rank, world)
+    last_out[0] = None
     if keep_global:
         del idx
     per_rank = [{"rank": rank, "users": [u0, u1], "nnz": nnz, "hop_ms_per_step":
@@ -925,7 +997,7 @@ def main():
                                  "into-items hops alone (gathering the user table; when blocked, "
                                  "dispatches_per_hop.into_items > 1, each dispatch's user slice "
                                  "is partly cache-resident too)")
-    if world == 1:
+    if world == 1 and args.full:
         # also report a measured stream-copy peak on this box (read + write bytes)
         cp, cp_detail = copy_peak_gbps(device)
         roofline["measured_copy_GBps"] = round(cp, 1)
@@ -1015,6 +1087,9 @@ def main():
         out["check"] = check
     if world == 1:
         out["parity"] = parity
+    out["full"] = bool(args.full)
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     print(json.dumps(out), flush=True)
     if parity is not None and not parity["ok"]:
         print(f"bench.py: PARITY FAILED against the reference's torch.sparse.mm on the same "

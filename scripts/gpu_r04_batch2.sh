@@ -21,7 +21,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_graph_step.py tests/test_gp
 HGD_DIST_BACKEND=gloo HGD_STALL_DUMP_S=200 timeout -k 10 300 python -u bench.py --gpus 2 --check \
     --no-cpu-baseline --pmc off --users 1000000 --items 100000 --edges 10000000 --steps 3 \
     --warmup 1 > $O/auto_n2.json 2> $O/auto_n2.err && echo "auto n2 ok" && \
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err && echo "bench ok" && \
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err && echo "bench ok" && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
     python bench.py --no-cpu-baseline --pmc off > $O/bench_prof.json 2> $O/bench_prof.err && \
 find $O/prof -name '*kernel_stats.csv' -exec cp {} $O/bench_kernel_stats.csv \; && \

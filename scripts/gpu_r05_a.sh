@@ -21,7 +21,7 @@ tail -3 $O/pytest.txt
 [ $prc -eq 0 ] || [ $prc -eq 1 ] || exit $prc   # 1 = test failures: still run the table
 timeout -k 10 300 python -u scripts/diag/diag_view_ratio.py > $O/seed_ratios.jsonl 2> $O/seed_ratios.err && \
 echo "ratios ok" && \
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err
 rc=$?
 echo "bench rc=$rc"; tail -c 1500 $O/bench.json
 exit $(( rc ? rc : prc ))

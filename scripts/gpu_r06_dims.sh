@@ -12,9 +12,9 @@ HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 timeout -k 10 200 python -u scripts/bench_mall_blocked.py --dim 32 --blocks 2,3,4 \
     > $O/ab_d32.json 2> $O/ab_d32.err && cat $O/ab_d32.json && \
-timeout -k 10 400 python -u bench.py --dim 32 --pmc off > $O/bench_d32.json 2> $O/bench_d32.err && \
+timeout -k 10 400 python -u bench.py --full --dim 32 --pmc off > $O/bench_d32.json 2> $O/bench_d32.err && \
 cat $O/bench_d32.json && \
-timeout -k 10 500 python -u bench.py --dim 128 --pmc off > $O/bench_d128.json 2> $O/bench_d128.err && \
+timeout -k 10 500 python -u bench.py --full --dim 128 --pmc off > $O/bench_d128.json 2> $O/bench_d128.err && \
 cat $O/bench_d128.json
 rc=$?
 echo "rc=$rc"

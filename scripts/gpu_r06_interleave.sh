@@ -18,7 +18,7 @@ timeout -k 10 300 python -u scripts/bench_pass_interleave.py --dim 256 > $O/ab_d
     2> $O/ab_d256.err && cat $O/ab_d256.json && \
 timeout -k 10 300 python -u scripts/bench_pass_interleave.py --dim 512 --edges 50000000 \
     > $O/ab_d512.json 2> $O/ab_d512.err && cat $O/ab_d512.json && \
-HGD_SPMM_PASS_INTERLEAVE=1 timeout -k 10 900 python -u bench.py --dim 256 \
+HGD_SPMM_PASS_INTERLEAVE=1 timeout -k 10 900 python -u bench.py --full --dim 256 \
     > $O/bench_d256_interleave.json 2> $O/bench_d256_interleave.err && echo "bench ok" && \
 tail -c 1500 $O/bench_d256_interleave.json
 rc=$?

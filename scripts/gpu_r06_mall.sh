@@ -19,7 +19,7 @@ timeout -k 10 300 python -u scripts/bench_mall_blocked.py --dim 128 --blocks 6,8
     > $O/d128.json 2> $O/d128.err && cat $O/d128.json && \
 timeout -k 10 400 python -u scripts/bench_mall_blocked.py --dim 256 --blocks 3,4,5,6 \
     --rounds 3 > $O/d256.json 2> $O/d256.err && cat $O/d256.json && \
-timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err && cat $O/bench.json
+timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err && cat $O/bench.json
 rc=$?
 echo "rc=$rc"
 exit $rc

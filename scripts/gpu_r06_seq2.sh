@@ -20,7 +20,7 @@ run hgd_torch_tail --hop1 hgd --hop2 torch --tail && \
 run hgd_hgd_chunks1 --hop1 hgd --hop2 hgd --chunks 1 && \
 run hgd_hgd_world4 --hop1 hgd --hop2 hgd --world 4 && \
 run hgd_hgd_sync --hop1 hgd --hop2 hgd --sync && \
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err && echo "bench ok" && \
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err && echo "bench ok" && \
 cat $O/bench.json
 rc=$?
 echo "rc=$rc"

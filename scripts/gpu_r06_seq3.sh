@@ -24,7 +24,7 @@ run gather_torch --hop1 gather --hop2 torch && \
 HIP_FORCE_DEV_KERNARG=0 run hgd_hgd_hostkernarg --hop1 hgd --hop2 hgd && \
 HSA_ENABLE_SDMA=0 run hgd_hgd_nosdma --hop1 hgd --hop2 hgd && \
 run hgd_hgd_sync --hop1 hgd --hop2 hgd --sync && \
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err && echo "bench ok" && \
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err && echo "bench ok" && \
 cat $O/bench.json
 rc=$?
 echo "rc=$rc"

@@ -18,7 +18,7 @@ grep -v '"mode"' $O/roundtrip_1proc.jsonl && \
 timeout -k 10 300 python -u scripts/diag/diag_stream_order.py --mode chunks --roundtrip \
     --producer hgd,gather --trials 30 --procs 8 > $O/roundtrip_8procs.jsonl \
     2> $O/roundtrip_8procs.err && grep -v '"mode"' $O/roundtrip_8procs.jsonl | grep "proc 0\]" && \
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err && echo "bench ok" && \
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err && echo "bench ok" && \
 cat $O/bench.json
 rc=$?
 echo "rc=$rc"

@@ -169,3 +169,33 @@ def test_host_cpus_reports_the_thread_choice():
     assert 1 <= h["threads"] <= h["affinity"]
     if h["cgroup_cpu_quota"]:
         assert h["threads"] <= h["cgroup_cpu_quota"]
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    plain = bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 4
+    full = bench.parse(["--full", "--dump-outputs", "out"])
+    assert full.full is True and full.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_all_rows_or_the_same_seeded_sample(tmp_path, monkeypatch):
+    g = torch.Generator().manual_seed(5)
+    Y, dX = torch.randn(1000, 16, generator=g), torch.randn(1000, 16, generator=g).double()
+    rec = bench.dump_outputs(str(tmp_path / "a"), {"Y": Y, "dX": dX})
+    got = np.load(tmp_path / "a" / "Y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, Y.numpy())
+    assert np.load(tmp_path / "a" / "dX.npy").dtype == np.float32
+    assert rec["files"]["Y.npy"] == {"shape": [1000, 16], "rows_of": 1000, "sampled": False}
+    # a budget of 100 rows per tensor: the same ascending sample for both, and in every run
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 100 * 16 * 4)
+    rec = bench.dump_outputs(str(tmp_path / "b"), {"Y": Y, "dX": dX})
+    bench.dump_outputs(str(tmp_path / "c"), {"Y": Y, "dX": dX})
+    Yb, dXb = np.load(tmp_path / "b" / "Y.npy"), np.load(tmp_path / "b" / "dX.npy")
+    assert Yb.shape == dXb.shape == (100, 16) and rec["files"]["dX.npy"]["sampled"]
+    rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(1000, size=100, replace=False))
+    assert np.array_equal(Yb, Y.numpy()[rows])
+    assert np.array_equal(dXb, dX.numpy()[rows].astype(np.float32))
+    assert np.array_equal(Yb, np.load(tmp_path / "c" / "Y.npy"))
+    # N > 1: every rank writes its own files, the budget shared
+    rec = bench.dump_outputs(str(tmp_path / "b"), {"Y": Y}, rank=1, world=2)
+    assert np.load(tmp_path / "b" / "Y_rank1.npy").shape == (100, 16)
