@@ -22,6 +22,7 @@ c_size = ctypes.c_size_t
 
 HGD_OK = 0
 EPI_NONE, EPI_LEAKY_RELU, EPI_RELU = 0, 1, 2
+DT_F32, DT_BF16 = 0, 1  # HGD_DT_*: element types of hgd_spmm_dt / hgd_spmm_masked_dt
 _STATUS_NAMES = {0: "HGD_OK", 1: "HGD_ERR_INVALID_ARG", 2: "HGD_ERR_HIP",
                  3: "HGD_ERR_UNSUPPORTED", 4: "HGD_ERR_WORKSPACE"}
 
@@ -229,6 +230,13 @@ _SIGNATURES = {
     "hgd_spmm": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64,
                          c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32, c_f32,
                          ctypes.POINTER(SplitPlan), c_void_p, c_size, c_void_p]),
+    "hgd_spmm_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64,
+                            c_void_p, c_i32, c_i64, c_void_p, c_i32, c_i64, c_i32, c_i32, c_f32,
+                            ctypes.POINTER(SplitPlan), c_void_p, c_size, c_void_p]),
+    "hgd_spmm_masked_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_void_p, c_i64,
+                                   c_i64, c_i64, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i32,
+                                   c_i64, c_i32, c_i32, c_f32, ctypes.POINTER(SplitPlan),
+                                   c_void_p, c_size, c_void_p]),
     "hgd_spmm_blocks_for": (c_i32, [c_i64, c_i32]),
     "hgd_spmm_col_blocks_workspace_size": (c_size, [c_i64, c_i32]),
     "hgd_spmm_col_blocks": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p,

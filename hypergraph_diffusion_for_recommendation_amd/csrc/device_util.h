@@ -24,7 +24,7 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
-// VEC contiguous floats (one 16-byte access when VEC == 4; NT = non-temporal).
+// VEC contiguous floats (one 16-byte access when VEC == 4, two when VEC == 8; NT = non-temporal).
 template <int VEC, bool NT = false>
 __device__ __forceinline__ void load_vec(const float* p, float (&v)[VEC]) {
   if constexpr (VEC == 4) {
@@ -34,6 +34,11 @@ __device__ __forceinline__ void load_vec(const float* p, float (&v)[VEC]) {
     else
       t = *reinterpret_cast<const f32x4*>(p);
     v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else if constexpr (VEC == 8) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+    const f32x4 u = *reinterpret_cast<const f32x4*>(p + 4);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    v[4] = u.x; v[5] = u.y; v[6] = u.z; v[7] = u.w;
   } else {
 #pragma unroll
     for (int i = 0; i < VEC; ++i) v[i] = p[i];
@@ -48,9 +53,58 @@ __device__ __forceinline__ void store_vec(float* p, const float (&v)[VEC]) {
       __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(p));
     else
       *reinterpret_cast<f32x4*>(p) = t;
+  } else if constexpr (VEC == 8) {
+    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
   } else {
 #pragma unroll
     for (int i = 0; i < VEC; ++i) p[i] = v[i];
+  }
+}
+
+// bfloat16 as stored in memory: the upper 16 bits of an fp32. Widening is exact (a shift); the
+// narrowing rounds to nearest even, as torch.Tensor.to(torch.bfloat16) does (NaN → quiet NaN).
+struct bf16 {
+  uint16_t bits;
+};
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float bf16_widen(uint32_t bits) { return __uint_as_float(bits << 16); }
+
+__device__ __forceinline__ uint32_t bf16_round(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;  // NaN
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+// VEC contiguous bf16 widened to floats (one 16-byte access when VEC == 8).
+template <int VEC, bool NT = false>
+__device__ __forceinline__ void load_vec(const bf16* p, float (&v)[VEC]) {
+  if constexpr (VEC == 8) {
+    const u32x4 t = *reinterpret_cast<const u32x4*>(p);
+    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
+    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
+    v[4] = __uint_as_float(t.z << 16); v[5] = __uint_as_float(t.z & 0xffff0000u);
+    v[6] = __uint_as_float(t.w << 16); v[7] = __uint_as_float(t.w & 0xffff0000u);
+  } else {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) v[i] = bf16_widen(p[i].bits);
+  }
+}
+
+// VEC floats rounded to bf16 (round-to-nearest-even) and stored (one 16-byte access when VEC == 8).
+template <int VEC, bool NT = false>
+__device__ __forceinline__ void store_vec(bf16* p, const float (&v)[VEC]) {
+  if constexpr (VEC == 8) {
+    const u32x4 t = {bf16_round(v[0]) | (bf16_round(v[1]) << 16),
+                     bf16_round(v[2]) | (bf16_round(v[3]) << 16),
+                     bf16_round(v[4]) | (bf16_round(v[5]) << 16),
+                     bf16_round(v[6]) | (bf16_round(v[7]) << 16)};
+    *reinterpret_cast<u32x4*>(p) = t;
+  } else {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) p[i].bits = static_cast<uint16_t>(bf16_round(v[i]));
   }
 }
 

@@ -69,6 +69,11 @@ struct SumRowsJob {
 };
 hgd_status sum_rows_jobs(const SumRowsJob* jobs, int n, hipStream_t st);
 
+// Tuning state of the hop that spmm.hip owns and spmm_dt.hip reads: HGD_TUNE_MASK_PAIR,
+// HGD_TUNE_MASK_DIV and HGD_TUNE_SPMM_PASS_COLS (0 = auto).
+extern int g_mask_pair;
+extern int g_mask_div;
+int spmm_pass_cols();
 // HGD_TUNE_ROWGEMM_BLOCKS (linear.hip): 0 restores the default.
 void set_row_gemm_max_blocks(int blocks);
 // HGD_TUNE_SPLITK_ROWS (linear.hip): rows per split-K slice, 0 restores the sizing rule.

@@ -37,6 +37,11 @@ _EPI = {None: nat.EPI_NONE, "none": nat.EPI_NONE, "leaky_relu": nat.EPI_LEAKY_RE
 
 
 def _epilogue_backward(ref: torch.Tensor, dy: torch.Tensor, epi: int, slope: float):
+    if ref.dtype != torch.float32 or dy.dtype != torch.float32:
+        # a 16-bit side (the bf16 hop): a streaming pass, not the hot path — the same select in
+        # torch ops (hgd_epilogue_backward is fp32)
+        other = dy * slope if epi == nat.EPI_LEAKY_RELU else torch.zeros_like(dy)
+        return torch.where(ref > 0, dy, other)
     ref = ref.contiguous()
     dy = dy.contiguous()
     dz = torch.empty_like(dy)
@@ -48,6 +53,9 @@ def _epilogue_backward(ref: torch.Tensor, dy: torch.Tensor, epi: int, slope: flo
 
 
 def _epilogue_apply(z: torch.Tensor, epi: int, slope: float):
+    if z.dtype != torch.float32:  # (as above)
+        other = z * slope if epi == nat.EPI_LEAKY_RELU else torch.zeros_like(z)
+        return torch.where(z > 0, z, other)
     y = torch.empty_like(z)
     nat.check(nat.load().hgd_epilogue_apply(z.data_ptr(), z.numel(), epi, float(slope),
                                             y.data_ptr(),
@@ -58,43 +66,49 @@ def _epilogue_apply(z: torch.Tensor, epi: int, slope: float):
 
 class _SpMM(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, X, inc: Incidence, transpose: bool):
+    def forward(ctx, X, inc: Incidence, transpose: bool, out_dtype=None):
         ctx.inc = inc
         ctx.transpose = transpose
+        ctx.x_dtype = X.dtype
         X = X.contiguous()
         if transpose:
-            return spmm_csr(inc.csc, X, val=inc.val_t)
-        return spmm_csr(inc.csr, X, val=inc.val)
+            return spmm_csr(inc.csc, X, val=inc.val_t, out_dtype=out_dtype)
+        return spmm_csr(inc.csr, X, val=inc.val, out_dtype=out_dtype)
 
     @staticmethod
     def backward(ctx, dY):
         inc = ctx.inc
         dY = dY.contiguous()
         if ctx.transpose:
-            dX = spmm_csr(inc.csr, dY, val=inc.val)
+            dX = spmm_csr(inc.csr, dY, val=inc.val, out_dtype=ctx.x_dtype)
         else:
-            dX = spmm_csr(inc.csc, dY, val=inc.val_t)
-        return dX, None, None
+            dX = spmm_csr(inc.csc, dY, val=inc.val_t, out_dtype=ctx.x_dtype)
+        return dX, None, None, None
 
 
-def spmm(inc: Incidence, X: torch.Tensor, transpose: bool = False) -> torch.Tensor:
-    """``A·X`` (or ``Aᵀ·X``) with autograd; ``torch.sparse.mm(adj, X)`` drop-in."""
-    return _SpMM.apply(X, inc, transpose)
+def spmm(inc: Incidence, X: torch.Tensor, transpose: bool = False,
+         out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``A·X`` (or ``Aᵀ·X``) with autograd; ``torch.sparse.mm(adj, X)`` drop-in. ``X`` is
+    float32 or bfloat16 (fp32 sums either way); the result is ``out_dtype`` or ``X.dtype``, the
+    gradient arrives in the result's dtype and leaves in ``X``'s."""
+    return _SpMM.apply(X, inc, transpose, out_dtype)
 
 
 class _TwoHop(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, X, inc: Incidence, P, Q, R, epi: int, slope: float):
+    def forward(ctx, X, inc: Incidence, P, Q, R, epi: int, slope: float, out_dtype=None):
         X = X.contiguous()
+        ctx.x_dtype = X.dtype
         q = inc.scale("col", Q)
-        # hop 1 into the columns (hyperedges) of A: M = Q·Aᵀ·(R·X)
+        # hop 1 into the columns (hyperedges) of A: M = Q·Aᵀ·(R·X), stored in X's dtype (a bf16
+        # table gives a bf16 M: the second hop's gather is halved too)
         M = spmm_csr(inc.csc, X, val=inc.edge_values("csc", R), row_scale=q)
         # hop 2 back into the rows (vertices): Z = P·A·M, epilogue fused when the sign test on
         # the output is equivalent to the one on the pre-activation (slope >= 0)
         p = inc.scale("row", P)
         fuse = epi != nat.EPI_NONE and slope >= 0.0
         Y = spmm_csr(inc.csr, M, val=inc.val, row_scale=p, epilogue=epi if fuse else 0,
-                     slope=slope)
+                     slope=slope, out_dtype=out_dtype)
         ref = Y
         if epi != nat.EPI_NONE and not fuse:
             ref = Y
@@ -116,27 +130,36 @@ class _TwoHop(torch.autograd.Function):
             (ref,) = ctx.saved_tensors
             dZ = _epilogue_backward(ref, dZ, ctx.epi, ctx.slope)
         q = inc.scale("col", Q)
-        dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q)
+        # dM in the dtype M had (X's), dX in X's
+        dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q,
+                      out_dtype=ctx.x_dtype)
         r = inc.scale("row", R)
-        dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=r)
-        return dX, None, None, None, None, None, None
+        dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=r, out_dtype=ctx.x_dtype)
+        return dX, None, None, None, None, None, None, None
 
 
 def two_hop(inc: Incidence, X: torch.Tensor, P: Optional[str] = None, Q: Optional[str] = None,
             R: Optional[str] = None, epilogue: Optional[str] = None,
-            slope: float = 0.0) -> torch.Tensor:
-    """``epi(P·A·Q·Aᵀ·R·X)`` with autograd (see module docstring for the scale names)."""
-    return _TwoHop.apply(X, inc, P, Q, R, _EPI[epilogue], float(slope))
+            slope: float = 0.0, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``epi(P·A·Q·Aᵀ·R·X)`` with autograd (see module docstring for the scale names).
+
+    ``X`` is float32 or bfloat16; the result is ``out_dtype`` or ``X.dtype``. With a bfloat16
+    ``X`` the intermediate M (and the backward's dM) is stored in bfloat16; all sums are fp32.
+    With fp32 master weights: ``two_hop(inc, E.bfloat16(), out_dtype=torch.float32)`` — autograd's
+    cast returns an fp32 gradient."""
+    return _TwoHop.apply(X, inc, P, Q, R, _EPI[epilogue], float(slope), out_dtype)
 
 
-def hgconv2(inc: Incidence, X: torch.Tensor) -> torch.Tensor:
+def hgconv2(inc: Incidence, X: torch.Tensor,
+            out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """HGNN normalised 2-hop ``D_v^-1/2·H·D_e^-1·Hᵀ·D_v^-1/2·X`` (data/graph.py:28-42)."""
-    return two_hop(inc, X, P="sym", Q="mean", R="sym")
+    return two_hop(inc, X, P="sym", Q="mean", R="sym", out_dtype=out_dtype)
 
 
-def mean2hop(inc: Incidence, X: torch.Tensor) -> torch.Tensor:
+def mean2hop(inc: Incidence, X: torch.Tensor,
+             out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """ED-HNN edge-mean then vertex-mean ``D_v^-1·B·D_e^-1·Bᵀ·X`` (EquivSetConv2.py:88-93)."""
-    return two_hop(inc, X, P="mean", Q="mean", R=None)
+    return two_hop(inc, X, P="mean", Q="mean", R=None, out_dtype=out_dtype)
 
 
 def _ln_supported(d: int) -> bool:
@@ -239,6 +262,10 @@ def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
     dim (its weight/bias get gradients). Shapes the fused store cannot hold (LayerNorm with
     d > 256, or a negative slope) run the same math as separate device ops."""
     epi = _EPI[epilogue]
+    for t in (X, res1, res2):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"two_hop_fused: float32 only (the fused row epilogue has no 16-bit "
+                            f"form), got {t.dtype}; use two_hop for a bfloat16 table")
     d = X.shape[1]
     ln = norm is not None
     if ln and (tuple(norm.normalized_shape) != (d,)):

@@ -241,12 +241,23 @@ def spmm_blocks(csr: CSR, d: int) -> int:
     return int(nat.load().hgd_spmm_blocks_for(csr.n_cols, int(d)))
 
 
+# element types of the hop's table and output -> HGD_DT_* (hgd_spmm_dt)
+_HOP_DTYPES = {torch.float32: nat.DT_F32, torch.bfloat16: nat.DT_BF16}
+
+
 def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
              row_scale: Optional[torch.Tensor] = None, epilogue: int = nat.EPI_NONE,
              slope: float = 0.0, out: Optional[torch.Tensor] = None,
              row_begin: int = 0, row_end: Optional[int] = None,
-             ex: Optional[nat.RowEpilogue] = None, blocks: Optional[int] = None) -> torch.Tensor:
+             ex: Optional[nat.RowEpilogue] = None, blocks: Optional[int] = None,
+             out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """``Y[r] = epi(row_scale[r] * Σ_e val[e] * X[col[e]])`` for r in [row_begin, row_end).
+
+    ``X`` is float32 or bfloat16; the result is ``out.dtype`` if ``out`` is given, else
+    ``out_dtype``, else ``X.dtype``. Float32 in and out is hgd_spmm (and its masked / blocked /
+    fused forms); a bfloat16 side is hgd_spmm_dt / hgd_spmm_masked_dt: the same fp32 sums over
+    exactly widened elements, a bf16 result rounded to nearest even on the store. A bf16 hop has
+    no fused row epilogue (``ex``) and never runs source-blocked.
 
     With ``ex`` (an ``hgd_row_epilogue``) the call is ``hgd_spmm_fused``: ``ex.act``/``ex.slope``
     replace ``epilogue``/``slope`` and the LayerNorm / residual epilogue runs in the store.
@@ -255,8 +266,15 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     would read back P−1 times)."""
     if X.dim() != 2:
         raise ValueError(f"spmm: X must be 2-D, got {tuple(X.shape)}")
-    if X.dtype != torch.float32:
-        raise TypeError(f"spmm: X must be float32, got {X.dtype}")
+    if X.dtype not in _HOP_DTYPES:
+        raise TypeError(f"spmm: X must be float32 or bfloat16, got {X.dtype}")
+    y_dtype = out.dtype if out is not None else (out_dtype or X.dtype)
+    if y_dtype not in _HOP_DTYPES:
+        raise TypeError(f"spmm: the output must be float32 or bfloat16, got {y_dtype}")
+    dt = X.dtype != torch.float32 or y_dtype != torch.float32  # a 16-bit side: the _dt entries
+    if dt and ex is not None:
+        raise TypeError("spmm: the fused row epilogue (ex=) is float32-only; a bfloat16 "
+                        f"table or output cannot take it (X {X.dtype}, output {y_dtype})")
     if X.device.type != "cuda":
         raise RuntimeError("spmm: X must be a device (cuda/hip) tensor; there is no CPU path")
     if X.shape[0] != csr.n_cols:
@@ -265,7 +283,7 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
         X = X.contiguous()
     d = X.shape[1]
     if out is None:
-        out = torch.empty((csr.n_rows, d), dtype=torch.float32, device=X.device)
+        out = torch.empty((csr.n_rows, d), dtype=y_dtype, device=X.device)
     if row_end is None:
         row_end = csr.n_rows
     if d == 0 or row_end <= row_begin:
@@ -285,11 +303,26 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     if timer is not None:
         t0 = timer.begin()
     mask = getattr(csr, "mask", None)
-    if mask is not None or ex is not None or blocks == 0:
-        blocks = 0
+    if mask is not None or ex is not None or blocks == 0 or dt:
+        blocks = 0  # (the size rule was measured for fp32 tables: a 16-bit hop is never blocked)
     else:
         blocks = spmm_blocks(csr, d)
-    if mask is not None and ex is not None:
+    if dt and mask is not None:
+        nat.check(lib.hgd_spmm_masked_dt(
+            csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None, nat.ptr(val),
+            mask.data_ptr() if csr.nnz else None, float(csr.keep), nat.ptr(row_scale),
+            csr.n_rows, csr.n_cols, int(row_begin), int(row_end), X.data_ptr(),
+            _HOP_DTYPES[X.dtype], X.stride(0), out.data_ptr(), _HOP_DTYPES[y_dtype],
+            out.stride(0), d, int(epilogue), float(slope), plan_ptr, nat.ptr(ws), wsb,
+            _stream(X.device)), "hgd_spmm_masked_dt")
+    elif dt:
+        nat.check(lib.hgd_spmm_dt(
+            csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None, nat.ptr(val),
+            nat.ptr(row_scale), csr.n_rows, csr.n_cols, int(row_begin), int(row_end),
+            X.data_ptr(), _HOP_DTYPES[X.dtype], X.stride(0), out.data_ptr(),
+            _HOP_DTYPES[y_dtype], out.stride(0), d, int(epilogue), float(slope), plan_ptr,
+            nat.ptr(ws), wsb, _stream(X.device)), "hgd_spmm_dt")
+    elif mask is not None and ex is not None:
         nat.check(lib.hgd_spmm_masked_fused(
             csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None, nat.ptr(val),
             mask.data_ptr() if csr.nnz else None, float(csr.keep), nat.ptr(row_scale),
@@ -328,10 +361,12 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
         full = rb == 0 and re_ == csr.n_rows
 
         def nbytes(csr=csr, rb=rb, re_=re_, full=full, d=d, hv=val is not None,
-                   hs=row_scale is not None, blocks=blocks):
+                   hs=row_scale is not None, blocks=blocks, xb=X.element_size(),
+                   yb=out.element_size()):
             nnz = csr.nnz if full else int(csr.rowptr[re_].item() - csr.rowptr[rb].item())
-            return (profiling.hop_bytes(nnz, re_ - rb, d),
-                    profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, blocks))
+            return (profiling.hop_bytes(nnz, re_ - rb, d, x_bytes=xb, y_bytes=yb),
+                    profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, blocks, x_bytes=xb,
+                                         y_bytes=yb))
 
         timer.end(t0, nbytes)
     return out

@@ -26,23 +26,27 @@ MODEL_NOTE = ("SURVEY.md §8d B_hop = nnz*(4+4d) + R*(4d+4) + (R+1)*4 (binary H;
               "implementation_bytes_per_launch)")
 
 
-def hop_bytes(nnz: int, rows: int, d: int, weighted: bool = False) -> int:
-    """SURVEY.md §8d algorithmic bytes of one hop (+4·nnz for an intrinsically weighted A)."""
-    return nnz * (4 + (4 if weighted else 0) + 4 * d) + rows * (4 * d + 4) + (rows + 1) * 4
+def hop_bytes(nnz: int, rows: int, d: int, weighted: bool = False, x_bytes: int = 4,
+              y_bytes: int = 4) -> int:
+    """SURVEY.md §8d algorithmic bytes of one hop (+4·nnz for an intrinsically weighted A);
+    ``x_bytes`` / ``y_bytes``: element sizes of the gathered table and of the output (2 = bf16):
+    B_hop(ex, ey) = nnz·(4 + ex·d) + R·(ey·d + 4) + (R+1)·4."""
+    return (nnz * (4 + (4 if weighted else 0) + x_bytes * d) + rows * (y_bytes * d + 4)
+            + (rows + 1) * 4)
 
 
 def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
-               blocks: int = 0) -> int:
+               blocks: int = 0, x_bytes: int = 4, y_bytes: int = 4) -> int:
     """Bytes the hgd_spmm launch streams at minimum as implemented (int64 rowptr, weights).
     A source-blocked hop (hgd_spmm_blocked, ``blocks`` = P > 1) reads the [R × (P+1)] int64
     block starts instead of the rowptr, writes every Y row P times, reads it back P−1 times and
     applies the row scale in every pass."""
     if blocks > 1:
-        return (nnz * (4 + (4 if has_val else 0) + 4 * d)
-                + rows * (4 * d * (2 * blocks - 1) + (4 * blocks if has_scale else 0))
+        return (nnz * (4 + (4 if has_val else 0) + x_bytes * d)
+                + rows * (y_bytes * d * (2 * blocks - 1) + (4 * blocks if has_scale else 0))
                 + rows * (blocks + 1) * 8)
-    return (nnz * (4 + (4 if has_val else 0) + 4 * d)
-            + rows * (4 * d + (4 if has_scale else 0)) + (rows + 1) * 8)
+    return (nnz * (4 + (4 if has_val else 0) + x_bytes * d)
+            + rows * (y_bytes * d + (4 if has_scale else 0)) + (rows + 1) * 8)
 
 
 class HopTimer:

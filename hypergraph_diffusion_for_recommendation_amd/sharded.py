@@ -129,6 +129,13 @@ def shard_rows_of_sorted_coo(indices: torch.Tensor, n_users: int, world: int, ra
 TRANSPORTS = ("rccl", "p2p")
 
 
+def _require_f32(t: torch.Tensor, what: str) -> None:
+    # the sharded hops and their exchange are float32-only (the one-device hop also takes
+    # bfloat16 tables: incidence.spmm_csr)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what}: the sharded hop is float32-only, got {t.dtype}")
+
+
 def _scale_of_degrees(deg: torch.Tensor, kind: str) -> torch.Tensor:
     """1/deg ('mean') or 1/sqrt(deg) ('sym') of float64 degrees, 0 where deg = 0, rounded to
     fp32: every step correctly rounded, so it is bitwise the library's hgd_degree_scale and the
@@ -587,6 +594,7 @@ class ShardedIncidence:
     def two_hop(self, X: torch.Tensor, src_kind: Optional[str],
                 dst_kind: Optional[str]) -> torch.Tensor:
         """``S_dst·H_g·Σ_ranks(Q·H_gᵀ·S_src·X_g)`` with the slice pipeline described above."""
+        _require_f32(X, "ShardedIncidence.two_hop")
         inc = self.inc
         d = X.shape[1]
         Y = torch.empty((inc.n_rows, d), dtype=torch.float32, device=X.device)
@@ -1056,6 +1064,7 @@ def bipartite_hop_fused(sh: "ShardedBipartite", X_local: torch.Tensor,
     layout (functional.two_hop_fused's store for the sharded hop); falls back to the separate
     row pass where the fused store cannot hold a row (LayerNorm with d > 256)."""
     from .functional import _EPI, _ln_supported, row_epilogue
+    _require_f32(X_local, "bipartite_hop_fused")
     if X_local.shape[0] != sh.n_local + sh.n_items:
         raise ValueError(f"bipartite_hop_fused: X has {X_local.shape[0]} rows, shard expects "
                          f"{sh.n_local} users + {sh.n_items} items")
@@ -1076,6 +1085,7 @@ def bipartite_hop_fused(sh: "ShardedBipartite", X_local: torch.Tensor,
 def bipartite_hop(sh: ShardedBipartite, X_local: torch.Tensor,
                   scale: Optional[str] = None) -> torch.Tensor:
     """``S·A·X`` on this rank's layout ``[X_u[u0:u1]; X_i]`` (see :class:`ShardedBipartite`)."""
+    _require_f32(X_local, "bipartite_hop")
     if X_local.shape[0] != sh.n_local + sh.n_items:
         raise ValueError(f"bipartite_hop: X has {X_local.shape[0]} rows, shard expects "
                          f"{sh.n_local} users + {sh.n_items} items")

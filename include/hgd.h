@@ -12,6 +12,7 @@
  *                                                               model/graph/HGCN.py:173-175,
  *                            torch_scatter.scatter(.., 'mean')  model/layers/layers2/EquivSetConv2.py:88-93
  *                            (row_scale = 1/count is the scatter-mean; val = per-nonzero weight)
+ *   hgd_spmm_dt              the same hops over bfloat16 tables (X and / or Y in 16 bits, fp32 sums)
  *   hgd_spmm_blocked         the same torch.sparse.mm(adj.t(), X) hop for a gathered table larger
  *                            than the Infinity Cache (source-blocked; hgd_spmm_col_blocks builds
  *                            its block-major copy of the CSC)
@@ -33,7 +34,8 @@
  *   - Errors come back as hgd_status; hgd_get_last_error_string() describes the last failure
  *     on the calling thread. No C++ exception crosses the ABI.
  *   - Indices: row pointers are int64, column/row indices are int32 (rows, cols < 2^31).
- *   - Floating point is fp32 in and out; sums run in fp32 in edge order (deterministic).
+ *   - Floating point is fp32 in and out (hgd_spmm_dt / hgd_spmm_masked_dt also take bfloat16
+ *     tables); sums run in fp32 in edge order (deterministic).
  */
 #ifndef HGD_H
 #define HGD_H
@@ -192,6 +194,37 @@ hgd_status hgd_spmm(const int64_t* rowptr, const int32_t* col, const float* val,
                     int64_t ldy, int32_t d, int32_t epilogue, float slope,
                     const hgd_split_plan* plan, void* workspace, size_t workspace_bytes,
                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same hop over tables stored in bfloat16. Replaces the same call sites as hgd_spmm
+ * (torch.sparse.mm(adj, X), model/graph/HCCF.py:199; torch.sparse.mm(adj.t(), X),
+ * model/graph/HGNN_HD4.py:459-462, model/graph/HGCN.py:173-175) when the embedding table is kept
+ * or staged in 16 bits: the gathered rows are nnz·2d of the hop's bytes instead of nnz·4d.
+ *   x_dtype / y_dtype: element type of X / Y (HGD_DT_F32 or HGD_DT_BF16); ldx / ldy count
+ *   elements of their own type. Pairs: bf16→bf16, bf16→f32, f32→bf16, and f32→f32, which forwards
+ *   to hgd_spmm / hgd_spmm_masked (bitwise theirs).
+ * A bf16 element is widened to fp32 exactly; the sum is hgd_spmm's (one fp32 fmaf chain in edge
+ * order, fp32 weights, row scales, split-row partials and activation); a bf16 Y is the fp32 result
+ * rounded to nearest even — the one new rounding. Workspace: hgd_spmm_workspace_size (unchanged:
+ * the partials are fp32). The 16-byte path needs d % 8 == 0 and 16-byte aligned rows on both sides
+ * (ld % 8 == 0 for bf16, % 4 for fp32); other shapes take the scalar path.
+ * ---------------------------------------------------------------------------------------- */
+#define HGD_DT_F32 0
+#define HGD_DT_BF16 1
+hgd_status hgd_spmm_dt(const int64_t* rowptr, const int32_t* col, const float* val,
+                       const float* row_scale, int64_t n_rows, int64_t n_src_rows,
+                       int64_t row_begin, int64_t row_end, const void* X, int32_t x_dtype,
+                       int64_t ldx, void* Y, int32_t y_dtype, int64_t ldy, int32_t d,
+                       int32_t epilogue, float slope, const hgd_split_plan* plan, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* hgd_spmm_masked (the edge-dropped view: mask, keep) with the same element types. */
+hgd_status hgd_spmm_masked_dt(const int64_t* rowptr, const int32_t* col, const float* val,
+                              const uint8_t* mask, float keep, const float* row_scale,
+                              int64_t n_rows, int64_t n_src_rows, int64_t row_begin,
+                              int64_t row_end, const void* X, int32_t x_dtype, int64_t ldx,
+                              void* Y, int32_t y_dtype, int64_t ldy, int32_t d, int32_t epilogue,
+                              float slope, const hgd_split_plan* plan, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The same hop (rows [row_begin,row_end), no split plan) run in n_blocks passes over SOURCE-ROW
