@@ -69,11 +69,24 @@ struct SumRowsJob {
 };
 hgd_status sum_rows_jobs(const SumRowsJob* jobs, int n, hipStream_t st);
 
-// Tuning state of the hop that spmm.hip owns and spmm_dt.hip reads: HGD_TUNE_MASK_PAIR,
-// HGD_TUNE_MASK_DIV and HGD_TUNE_SPMM_PASS_COLS (0 = auto).
-extern int g_mask_pair;
-extern int g_mask_div;
-int spmm_pass_cols();
+// Tuning knobs of the SpMM hop (hgd_set_tuning sets them, spmm_launch.h reads them); the defaults
+// are the measured best on MI355X.
+struct SpmmTuning {
+  int unroll = 8;  // HGD_TUNE_SPMM_UNROLL
+  int policy = 8;  // HGD_TUNE_SPMM_POLICY: kPolPrefetch (spmm_kernels.h)
+  // HGD_TUNE_SPMM_PASS_COLS: widest column pass of the vector path without a fused epilogue;
+  // 0 = auto (spmm_pass_plan's defaults)
+  int pass_cols = 0;
+  // HGD_TUNE_SPMM_PASS_INTERLEAVE: 1 = a wide row's column passes as ONE launch, interleaved so the
+  // passes of a row block run back to back on one XCD (see spmm_kernel); 0 = a launch per pass
+  int pass_interleave = 0;
+  // HGD_TUNE_SPMM_BLOCKED_SEG: 1 = the source-blocked hop walks each block's short rows with the
+  // segmented kernel (a group owns G consecutive rows as one nonzero stream); 0 = a row per group
+  int blocked_seg = 0;
+  int mask_pair = 2;  // HGD_TUNE_MASK_PAIR: the masked hop walks two index batches per step
+  int mask_div = 0;   // HGD_TUNE_MASK_DIV: 1 = divide by keep even when it is a power of two
+};
+SpmmTuning& spmm_tuning();  // (tuning.cpp)
 // HGD_TUNE_ROWGEMM_BLOCKS (linear.hip): 0 restores the default.
 void set_row_gemm_max_blocks(int blocks);
 // HGD_TUNE_SPLITK_ROWS (linear.hip): rows per split-K slice, 0 restores the sizing rule.

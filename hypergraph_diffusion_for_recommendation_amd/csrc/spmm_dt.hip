@@ -16,173 +16,14 @@
 // than 128 columns run as 128-column passes (256 B of a bf16 row per gathered piece, the size of
 // the fp32 hop's 64-column piece; HGD_TUNE_SPMM_PASS_COLS overrides it). Only the default cache
 // policy and U = 8 are instantiated here: the d = 64 tuning matrix stays fp32-only.
-#include <cmath>
-
-#include "spmm_kernels.h"
+//
+// The checks, the pass plan and the launches are the shared launcher's (spmm_launch.h), where
+// every difference from the fp32 hop is an explicit condition on the element types; this file is
+// the dtype-code dispatch onto its three mixed instantiations.
+#include "spmm_launch.h"
 
 namespace hgd {
 namespace {
-
-constexpr int kU = 8;
-constexpr int kPol = kPolPrefetch;
-
-template <int G, int VEC, class TX, class TY>
-void launch_rows(const SpmmArgsT<TX, TY>& a, bool has_val, bool seg, int64_t blocks,
-                 hipStream_t st) {
-  if (a.mask) {  // masked (edge-dropped view) hop: the row kernel only
-    if (has_val)
-      hipLaunchKernelGGL((spmm_kernel<G, VEC, kU, true, kPol, false, true, TX, TY>), dim3(blocks),
-                         dim3(kBlock), 0, st, a);
-    else
-      hipLaunchKernelGGL((spmm_kernel<G, VEC, kU, false, kPol, false, true, TX, TY>), dim3(blocks),
-                         dim3(kBlock), 0, st, a);
-    return;
-  }
-  if constexpr (G >= 8) {
-    if (seg) {
-      if (has_val)
-        hipLaunchKernelGGL((spmm_seg_kernel<G, VEC, kU, true, kPol, false, TX, TY>), dim3(blocks),
-                           dim3(kBlock), 0, st, a);
-      else
-        hipLaunchKernelGGL((spmm_seg_kernel<G, VEC, kU, false, kPol, false, TX, TY>),
-                           dim3(blocks), dim3(kBlock), 0, st, a);
-      return;
-    }
-  }
-  if (has_val)
-    hipLaunchKernelGGL((spmm_kernel<G, VEC, kU, true, kPol, false, false, TX, TY>), dim3(blocks),
-                       dim3(kBlock), 0, st, a);
-  else
-    hipLaunchKernelGGL((spmm_kernel<G, VEC, kU, false, kPol, false, false, TX, TY>), dim3(blocks),
-                       dim3(kBlock), 0, st, a);
-}
-
-// One column pass: the segmented walk, or the row kernel (split-row chunks first in the grid) and
-// the fix-up of the split rows — the launch shapes of spmm.hip's launch_g.
-template <int G, int VEC, class TX, class TY>
-hgd_status launch_g(SpmmArgsT<TX, TY> a, bool has_val, hipStream_t st) {
-  constexpr int GPB = kBlock / G;
-  const int64_t rows = a.row_end - a.row_begin;
-  if constexpr (G >= 8) {
-    if (a.seg) {
-      const int64_t sblocks = (rows + static_cast<int64_t>(GPB) * G - 1) / (GPB * G);
-      if (sblocks <= 0) return HGD_OK;
-      if (sblocks > 0x7fffffffLL) return fail(HGD_ERR_UNSUPPORTED, "hgd_spmm_dt: grid too large");
-      launch_rows<G, VEC>(a, has_val, true, sblocks, st);
-      return check_launch("hgd_spmm_dt segmented kernel");
-    }
-  }
-  a.heavy_blocks = (a.n_chunks + GPB - 1) / GPB;
-  const int64_t blocks = (rows + GPB - 1) / GPB + a.heavy_blocks;
-  if (blocks > 0) {
-    if (blocks > 0x7fffffffLL) return fail(HGD_ERR_UNSUPPORTED, "hgd_spmm_dt: grid too large");
-    launch_rows<G, VEC>(a, has_val, false, blocks, st);
-    hgd_status s = check_launch("hgd_spmm_dt kernel");
-    if (s != HGD_OK) return s;
-  }
-  if (a.n_heavy > 0) {
-    if (a.n_heavy > 0x7fffffffLL)
-      return fail(HGD_ERR_UNSUPPORTED, "hgd_spmm_dt: too many split rows");
-    hipLaunchKernelGGL((spmm_fixup_kernel<G, VEC, false, TX, TY>), dim3(a.n_heavy), dim3(kBlock),
-                       0, st, a);
-    return check_launch("hgd_spmm_dt fixup");
-  }
-  return HGD_OK;
-}
-
-template <int VEC, class TX, class TY>
-hgd_status launch_vec(int G, const SpmmArgsT<TX, TY>& a, bool has_val, hipStream_t st) {
-  switch (G) {
-    case 1: return launch_g<1, VEC>(a, has_val, st);
-    case 2: return launch_g<2, VEC>(a, has_val, st);
-    case 4: return launch_g<4, VEC>(a, has_val, st);
-    case 8: return launch_g<8, VEC>(a, has_val, st);
-    case 16: return launch_g<16, VEC>(a, has_val, st);
-    case 32: return launch_g<32, VEC>(a, has_val, st);
-    case 64:  // a pass of the 8-column path is at most 256 columns: 32 lanes
-      if constexpr (VEC == 1) return launch_g<64, VEC>(a, has_val, st);
-      [[fallthrough]];
-    default: return fail(HGD_ERR_UNSUPPORTED, "hgd_spmm_dt: unsupported group size %d", G);
-  }
-}
-
-template <class T>
-constexpr int64_t kVecElems = 16 / static_cast<int64_t>(sizeof(T));  // elements per 16 bytes
-
-template <class TX, class TY>
-hgd_status spmm_dt_impl(const int64_t* rowptr, const int32_t* col, const float* val,
-                        const float* row_scale, int64_t row_begin, int64_t row_end, const TX* X,
-                        int64_t ldx, TY* Y, int64_t ldy, int32_t d, int32_t epilogue, float slope,
-                        const uint8_t* mask, float keep, const hgd_split_plan* plan,
-                        void* workspace, size_t workspace_bytes, void* stream, const char* fn) {
-  SpmmArgsT<TX, TY> a{};
-  a.rowptr = rowptr;
-  a.col = col;
-  a.val = val;
-  a.row_scale = row_scale;
-  a.row_begin = row_begin;
-  a.row_end = row_end;
-  a.X = X;
-  a.ldx = ldx;
-  a.Y = Y;
-  a.ldy = ldy;
-  a.d = d;
-  a.epi = epilogue;
-  a.slope = slope;
-  a.mask = mask;
-  a.keep = keep;
-  {
-    int e2 = 0;
-    a.inv_keep = (!g_mask_div && keep > 0.f && std::frexp(keep, &e2) == 0.5f) ? 1.f / keep : 0.f;
-  }
-  a.mask_pair = g_mask_pair;
-  if (plan && plan->threshold > 0 && plan->n_heavy > 0) {
-    HGD_REQUIRE(plan->chunk > 0 && plan->heavy_rows && plan->heavy_cptr && plan->chunk_heavy,
-                "%s: incomplete split plan", fn);
-    const size_t need = hgd_spmm_workspace_size(plan, d);  // fp32 partials, as hgd_spmm's
-    if (workspace_bytes < need || (need && !workspace))
-      return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes,
-                  need);
-    a.heavy_threshold = plan->threshold;
-    a.chunk = plan->chunk;
-    a.n_chunks = plan->n_chunks;
-    a.n_heavy = plan->n_heavy;
-    a.chunk_heavy = plan->chunk_heavy;
-    a.heavy_rows = plan->heavy_rows;
-    a.heavy_cptr = plan->heavy_cptr;
-    a.partial = static_cast<float*>(workspace);
-  } else if (plan && (plan->flags & HGD_PLAN_SEGMENTED) && !mask) {
-    a.seg = 1;  // only without split rows: the segmented walk covers every nonzero of its rows
-  }
-
-  hipStream_t st = as_stream(stream);
-  const bool has_val = val != nullptr;
-  // 16-byte rows: a lane's 8 columns are one access of a bf16 row, two of an fp32 row
-  auto al16 = [](const void* p, int64_t ld, int64_t per16) {
-    return p == nullptr || (reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % per16 == 0);
-  };
-  const bool aligned = d % 8 == 0 && al16(X, ldx, kVecElems<TX>) && al16(Y, ldy, kVecElems<TY>);
-  if (aligned) {
-    const int lanes = d / 8;
-    int G = lanes >= 64 ? 64 : next_pow2(lanes);
-    const int tuned = spmm_pass_cols();
-    const int pass_cols = tuned ? tuned : 128;
-    if (8 * G > pass_cols) G = pass_cols / 8;
-    for (int c0 = 0; c0 < d; c0 += 8 * G) {
-      a.col0 = c0;
-      hgd_status s = launch_vec<8>(G, a, has_val, st);
-      if (s != HGD_OK) return s;
-    }
-  } else {
-    const int G = d >= 64 ? 64 : next_pow2(d);
-    for (int c0 = 0; c0 < d; c0 += G) {
-      a.col0 = c0;
-      hgd_status s = launch_vec<1>(G, a, has_val, st);
-      if (s != HGD_OK) return s;
-    }
-  }
-  return HGD_OK;
-}
 
 hgd_status spmm_dt_dispatch(const int64_t* rowptr, const int32_t* col, const float* val,
                             const float* row_scale, int64_t n_rows, int64_t n_src_rows,
@@ -191,30 +32,15 @@ hgd_status spmm_dt_dispatch(const int64_t* rowptr, const int32_t* col, const flo
                             int32_t epilogue, float slope, const uint8_t* mask, float keep,
                             const hgd_split_plan* plan, void* workspace, size_t workspace_bytes,
                             void* stream, const char* fn) {
-  HGD_REQUIRE(d > 0, "%s: d must be > 0 (got %d)", fn, d);
-  HGD_REQUIRE(n_rows >= 0 && n_src_rows >= 0, "%s: negative sizes", fn);
-  HGD_REQUIRE(row_begin >= 0 && row_begin <= row_end && row_end <= n_rows,
-              "%s: row range [%lld,%lld) outside [0,%lld)", fn, (long long)row_begin,
-              (long long)row_end, (long long)n_rows);
-  HGD_REQUIRE(ldx >= d && ldy >= d, "%s: ldx/ldy must be >= d", fn);
-  HGD_REQUIRE(epilogue >= HGD_EPI_NONE && epilogue <= HGD_EPI_RELU, "%s: bad epilogue %d", fn,
-              epilogue);
-  if (row_end == row_begin) return HGD_OK;
-  // col / X may be NULL for a structure without nonzeros (never dereferenced then).
-  HGD_REQUIRE(rowptr && Y, "%s: null rowptr/Y", fn);
-  HGD_REQUIRE(X || n_src_rows == 0, "%s: null X", fn);
+  auto hop = [&](auto* x, auto* y) {
+    return spmm_launch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end, x, ldx,
+                       y, ldy, d, epilogue, slope, nullptr, mask, keep, plan, workspace,
+                       workspace_bytes, stream, fn);
+  };
   const bool xb = x_dtype == HGD_DT_BF16, yb = y_dtype == HGD_DT_BF16;
-  if (xb && yb)
-    return spmm_dt_impl(rowptr, col, val, row_scale, row_begin, row_end,
-                        static_cast<const bf16*>(X), ldx, static_cast<bf16*>(Y), ldy, d, epilogue,
-                        slope, mask, keep, plan, workspace, workspace_bytes, stream, fn);
-  if (xb)
-    return spmm_dt_impl(rowptr, col, val, row_scale, row_begin, row_end,
-                        static_cast<const bf16*>(X), ldx, static_cast<float*>(Y), ldy, d, epilogue,
-                        slope, mask, keep, plan, workspace, workspace_bytes, stream, fn);
-  return spmm_dt_impl(rowptr, col, val, row_scale, row_begin, row_end,
-                      static_cast<const float*>(X), ldx, static_cast<bf16*>(Y), ldy, d, epilogue,
-                      slope, mask, keep, plan, workspace, workspace_bytes, stream, fn);
+  if (xb && yb) return hop(static_cast<const bf16*>(X), static_cast<bf16*>(Y));
+  if (xb) return hop(static_cast<const bf16*>(X), static_cast<float*>(Y));
+  return hop(static_cast<const float*>(X), static_cast<bf16*>(Y));
 }
 
 bool dtype_ok(int32_t dt) { return dt == HGD_DT_F32 || dt == HGD_DT_BF16; }

@@ -1,4 +1,4 @@
-// Device side of the CSR row-gather SpMM hop (spmm.hip, spmm_dt.hip): the argument block, the
+// Device side of the CSR row-gather SpMM hop (launched by spmm_launch.h): the argument block, the
 // gather walks and the kernels, templated on the element types of the gathered table (TX) and
 // of the output (TY). Not part of the ABI.
 #pragma once

@@ -36,3 +36,17 @@ def random_coo(rng, n_rows, n_cols, nnz, sort=True, dup=False):
         p = np.argsort(r, kind="stable")
         r, c = r[p], c[p]
     return r.astype(np.int64), c.astype(np.int64)
+
+
+def dispatch_graph(seed=0, n_rows=300, n_cols=257):
+    """The small graph of the hop's dispatch tests (tuning matrix, column passes): row-sorted COO
+    ``(rows, cols, vals)`` of ~2,300 nonzeros with empty rows (every 17th) and three rows long
+    enough to be split by a plan built with ``split_threshold=16`` (200, 90 and 33 nonzeros)."""
+    rng = np.random.default_rng(seed)
+    degs = rng.integers(0, 14, n_rows)
+    degs[::17] = 0
+    degs[5], degs[6], degs[n_rows - 1] = 200, 90, 33
+    rows = np.repeat(np.arange(n_rows), degs)
+    cols = np.concatenate([np.sort(rng.choice(n_cols, size=k, replace=False)) for k in degs])
+    vals = rng.standard_normal(len(rows)).astype(np.float32)
+    return rows.astype(np.int64), cols.astype(np.int64), vals

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import hgd_oracle as O
-from tests._util import assert_close, random_coo
+from tests._util import assert_close, dispatch_graph, random_coo
 
 pytestmark = pytest.mark.gpu
 
@@ -436,3 +436,152 @@ def test_spmm_blocks_zero_keeps_the_plain_hop(dev, monkeypatch):
     blocked = spmm_csr(inc.csc, X, val=inc.val_t)
     kept = spmm_csr(inc.csc, X, val=inc.val_t, blocks=0)
     assert torch.equal(kept, plain) and not torch.equal(blocked, plain)
+
+
+# hgd_set_tuning keys (include/hgd.h) and their defaults
+_UNROLL, _POLICY, _PASS_COLS = 1, 2, 3
+_GR, _GC = 300, 257  # dispatch_graph's shape
+
+
+def _set(lib, nat, key, value):
+    nat.check(lib.hgd_set_tuning(key, value), "hgd_set_tuning")
+
+
+def _plan_case(dev, kind, weighted):
+    """dispatch_graph under one of the three plans the d = 64 launch chain tells apart."""
+    rows, cols, vals = dispatch_graph(7)
+    if not weighted:
+        vals = None
+    if kind == "split":
+        inc = _build(rows, cols, vals, (_GR, _GC), dev, split_threshold=16, split_chunk=8)
+        assert inc.csr.n_heavy == 3 and not inc.csr.segmented
+    else:
+        inc = _build(rows, cols, vals, (_GR, _GC), dev, split_threshold=0)
+        inc.csr.configure_kernel(segmented=kind == "segmented")
+        assert inc.csr.n_heavy == 0 and inc.csr.segmented == (kind == "segmented")
+    return rows, cols, vals, inc
+
+
+@pytest.mark.parametrize("kind", ["rows", "segmented", "split"])
+@pytest.mark.parametrize("weighted", [False, True])
+def test_spmm_tuning_matrix_is_bitwise_the_default(dev, kind, weighted):
+    """HGD_TUNE_SPMM_UNROLL × HGD_TUNE_SPMM_POLICY at d = 64, the one width that carries the
+    matrix: every policy with unroll 8 and 16, over the row kernel, the segmented kernel and a
+    plan with split rows. The policy bits change only load / store hints and the unroll only how
+    many gathers are in flight; the sum is one fp32 fmaf chain in edge order either way, so every
+    variant is bitwise the default (policy 8, unroll 8), which itself is within the file's bound
+    of the float64 oracle."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr
+    lib = nat.load()
+    d = 64
+    rows, cols, vals, inc = _plan_case(dev, kind, weighted)
+    rng = np.random.default_rng(64 + weighted)
+    X = torch.from_numpy(rng.standard_normal((_GC, d)).astype(np.float32)).to(dev)
+    scale = rng.random(_GR).astype(np.float32)
+    s = torch.from_numpy(scale).to(dev)
+
+    def hop():
+        Y = torch.full((_GR, d), float("nan"), device=dev)
+        spmm_csr(inc.csr, X, val=inc.val, row_scale=s, epilogue=nat.EPI_LEAKY_RELU, slope=0.2,
+                 out=Y)
+        return Y
+
+    try:
+        _set(lib, nat, _UNROLL, 8)
+        _set(lib, nat, _POLICY, 8)
+        base = hop()
+        rowptr, col, v, _ = O.csr_from_coo(rows, cols, _GR, vals)
+        assert_close(base.cpu().numpy(),
+                     O.spmm_csr(rowptr, col, X.cpu().numpy(), v, scale, epi="leaky_relu",
+                                slope=0.2),
+                     O.spmm_csr(rowptr, col, X.cpu().numpy(), v, scale, absolute=True),
+                     what=f"default tuning, {kind}")
+        for policy in (0, 1, 8, 9, 10, 11):
+            for unroll in (8, 16):
+                _set(lib, nat, _POLICY, policy)
+                _set(lib, nat, _UNROLL, unroll)
+                assert torch.equal(hop(), base), (kind, weighted, policy, unroll)
+    finally:
+        _set(lib, nat, _UNROLL, 8)
+        _set(lib, nat, _POLICY, 8)
+
+
+@pytest.mark.parametrize("d", [320, 128])
+def test_spmm_pass_cols_is_bitwise_auto(dev, monkeypatch, d):
+    """HGD_TUNE_SPMM_PASS_COLS ∈ {64, 128, 256} against 0 (auto): column passes are independent,
+    so the width of a pass changes no bit — the plain hop in both orientations and the
+    source-blocked hop with 2 blocks. Rows are whole here: the fix-up of a split row adds its
+    chunk partials in an order fixed by (chunk count, groups per block), and the groups per block
+    follow the pass width. The auto output is checked against the float64 oracle."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr
+    from hypergraph_diffusion_for_recommendation_amd.incidence import spmm_blocks
+    lib = nat.load()
+    rows, cols, vals, whole = _plan_case(dev, "rows", True)
+    rng = np.random.default_rng(d)
+    X = torch.from_numpy(rng.standard_normal((_GC, d)).astype(np.float32)).to(dev)
+    Xt = torch.from_numpy(rng.standard_normal((_GR, d)).astype(np.float32)).to(dev)
+    scale = rng.random(_GR).astype(np.float32)
+    s = torch.from_numpy(scale).to(dev)
+
+    def hops():
+        Y = torch.full((_GR, d), float("nan"), device=dev)
+        spmm_csr(whole.csr, X, val=whole.val, row_scale=s, out=Y)
+        monkeypatch.setenv("HGD_SPMM_BLOCKS", "0")
+        plain_t = spmm_csr(whole.csc, Xt, val=whole.val_t)
+        monkeypatch.setenv("HGD_SPMM_BLOCKS", "2")
+        assert spmm_blocks(whole.csc, d) == 2
+        Yb = torch.full((_GC, d), float("nan"), device=dev)
+        spmm_csr(whole.csc, Xt, val=whole.val_t, out=Yb)
+        return Y, plain_t, Yb
+
+    try:
+        _set(lib, nat, _PASS_COLS, 0)
+        base = hops()
+        for pass_cols in (64, 128, 256):
+            _set(lib, nat, _PASS_COLS, pass_cols)
+            for i, (got, want) in enumerate(zip(hops(), base)):
+                assert torch.equal(got, want), (d, pass_cols, i)
+    finally:
+        _set(lib, nat, _PASS_COLS, 0)
+    rowptr, col, v, _ = O.csr_from_coo(rows, cols, _GR, vals)
+    assert_close(base[0].cpu().numpy(), O.spmm_csr(rowptr, col, X.cpu().numpy(), v, scale),
+                 O.spmm_csr(rowptr, col, X.cpu().numpy(), v, scale, absolute=True),
+                 what=f"pass cols auto d={d}")
+    Xtn = Xt.cpu().numpy()
+    ref_t = O.spmm_coo(cols, rows, vals, _GC, Xtn)
+    mag_t = O.spmm_coo(cols, rows, np.abs(vals), _GC, np.abs(Xtn))
+    assert_close(base[1].cpu().numpy(), ref_t, mag_t, what=f"pass cols auto Aᵀ d={d}")
+    assert_close(base[2].cpu().numpy(), ref_t, mag_t, what=f"pass cols auto blocked d={d}")
+
+
+def test_spmm_masked_and_fused_hops_ignore_the_tuning_matrix(dev):
+    """The masked hop and the fused-epilogue hop at d = 64 run U = 8 with the prefetch policy
+    whatever HGD_TUNE_SPMM_UNROLL / HGD_TUNE_SPMM_POLICY say: bitwise their default-tuning
+    output with unroll 16 and policy 1 set."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr
+    lib = nat.load()
+    d = 64
+    rows, cols, vals, inc = _plan_case(dev, "split", True)
+    rng = np.random.default_rng(99)
+    X = torch.from_numpy(rng.standard_normal((_GC, d)).astype(np.float32)).to(dev)
+    view = inc.masked(torch.from_numpy((rng.random(len(rows)) < 0.5).astype(np.uint8)), 0.5)
+    ex = nat.RowEpilogue(act=nat.EPI_LEAKY_RELU, slope=0.2, layer_norm=1, ln_eps=1e-5,
+                         out_scale=1.0)
+
+    def hops():
+        return (spmm_csr(view.csr, X, val=view.val),
+                spmm_csr(inc.csr, X, val=inc.val, ex=ex))
+
+    try:
+        base = hops()
+        assert all(bool(torch.isfinite(y).all()) and bool(y.abs().sum() > 0) for y in base)
+        _set(lib, nat, _UNROLL, 16)
+        _set(lib, nat, _POLICY, 1)
+        for got, want in zip(hops(), base):
+            assert torch.equal(got, want)
+    finally:
+        _set(lib, nat, _UNROLL, 8)
+        _set(lib, nat, _POLICY, 8)

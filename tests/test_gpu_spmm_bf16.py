@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from oracle import hgd_oracle as O
-from tests._util import assert_close, random_coo
+from tests._util import assert_close, dispatch_graph, random_coo
 
 pytestmark = pytest.mark.gpu
 
@@ -319,3 +319,64 @@ def test_dt_entry_with_f32_codes_is_bitwise_hgd_spmm(dev, d, split):
     assert not a.isnan().any() and torch.equal(a, b)
     assert torch.equal(a, spmm_csr(inc.csr, X, val=inc.val, row_scale=s))
     assert torch.equal(a, spmm_csr(inc.csr, X, val=inc.val, row_scale=s, out_dtype=F32))
+
+
+@pytest.mark.parametrize("d", [320, 136])
+@pytest.mark.parametrize("y_dtype", [BF16, F32])
+def test_bf16_pass_cols_is_bitwise_auto(dev, d, y_dtype):
+    """HGD_TUNE_SPMM_PASS_COLS ∈ {64, 128, 256} against 0 (auto, 128 with a 16-bit side) over a
+    bf16 table: column passes are independent, so the width of a pass changes no bit. d = 136 is
+    aligned but no multiple of a pass. Rows are whole here: a split row's fix-up adds its chunk
+    partials in an order that follows the groups per block, hence the pass width. The auto output
+    obeys the file's bounds."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr
+    lib = nat.load()
+    rows, cols, vals = dispatch_graph(7)
+    R, C = 300, 257
+    inc = _build(rows, cols, vals, (R, C), dev, split_threshold=0)
+    assert inc.csr.n_heavy == 0
+    rng = np.random.default_rng(d)
+    X, Xr = _bf16_table(rng, (C, d), dev)
+    scale = rng.random(R).astype(np.float32)
+    s = torch.from_numpy(scale).to(dev)
+
+    def hop():
+        Y = torch.full((R, d), float("nan"), dtype=y_dtype, device=dev)
+        spmm_csr(inc.csr, X, val=inc.val, row_scale=s, out=Y)
+        return Y
+
+    try:
+        nat.check(lib.hgd_set_tuning(3, 0), "hgd_set_tuning")
+        base = hop()
+        for pass_cols in (64, 128, 256):
+            nat.check(lib.hgd_set_tuning(3, pass_cols), "hgd_set_tuning")
+            assert torch.equal(hop(), base), (d, y_dtype, pass_cols)
+    finally:
+        nat.check(lib.hgd_set_tuning(3, 0), "hgd_set_tuning")
+    Y32 = _both(inc.csr, X, val=inc.val, row_scale=s)
+    assert torch.equal(base, Y32.to(y_dtype))
+    rowptr, col, v, _ = O.csr_from_coo(rows, cols, R, vals)
+    assert_close(Y32.cpu().numpy(), O.spmm_csr(rowptr, col, Xr, v, scale),
+                 O.spmm_csr(rowptr, col, Xr, v, scale, absolute=True),
+                 what=f"bf16 pass cols auto d={d}")
+
+
+def test_bf16_hop_ignores_the_tuning_matrix(dev):
+    """A bf16 hop at d = 64 runs U = 8 with the prefetch policy whatever HGD_TUNE_SPMM_UNROLL /
+    HGD_TUNE_SPMM_POLICY say: bitwise its default-tuning output with unroll 16 and policy 1."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    lib = nat.load()
+    rows, cols, vals = dispatch_graph(7)
+    R, C, d = 300, 257, 64
+    inc = _build(rows, cols, vals, (R, C), dev, split_threshold=16, split_chunk=8)
+    X, _ = _bf16_table(np.random.default_rng(64), (C, d), dev)
+    try:
+        base = _both(inc.csr, X, val=inc.val)
+        assert bool(base.abs().sum() > 0)
+        nat.check(lib.hgd_set_tuning(1, 16), "hgd_set_tuning")
+        nat.check(lib.hgd_set_tuning(2, 1), "hgd_set_tuning")
+        assert torch.equal(_both(inc.csr, X, val=inc.val), base)
+    finally:
+        nat.check(lib.hgd_set_tuning(1, 8), "hgd_set_tuning")
+        nat.check(lib.hgd_set_tuning(2, 8), "hgd_set_tuning")
