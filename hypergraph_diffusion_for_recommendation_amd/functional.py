@@ -687,6 +687,21 @@ def layer_norm(x: torch.Tensor, norm: torch.nn.LayerNorm) -> torch.Tensor:
                                           norm.eps)
 
 
+def _nce_table(E: torch.Tensor) -> torch.Tensor:
+    """``E`` itself when the InfoNCE gather can read it in place through its leading dimension
+    (float4 loads: unit column stride, a 16-byte aligned base, rows a multiple of four floats
+    apart and at least d), otherwise a compact copy — a column slice such as ``T[:, 2:66]`` is
+    a valid table, not an error."""
+    d = E.shape[1]
+    if (E.stride(1) == 1 and E.stride(0) % 4 == 0 and E.stride(0) >= d
+            and E.data_ptr() % 16 == 0):
+        return E
+    Ec = E.contiguous()
+    if Ec.stride(0) != d or Ec.data_ptr() % 16:  # a one-row view counts as contiguous as it is
+        Ec = Ec.clone(memory_format=torch.contiguous_format)
+    return Ec
+
+
 class _ContrastLoss(torch.autograd.Function):
     """hgd_infonce_forward / hgd_infonce_backward (see contrast_loss)."""
 
@@ -694,8 +709,7 @@ class _ContrastLoss(torch.autograd.Function):
     def forward(ctx, E1, E2, nodes, temp: float, count=None):
         lib = nat.load()
         dev = E1.device
-        E1c = E1 if E1.stride(1) == 1 else E1.contiguous()
-        E2c = E2 if E2.stride(1) == 1 else E2.contiguous()
+        E1c, E2c = _nce_table(E1), _nce_table(E2)
         nodes = nodes.to(device=dev, dtype=torch.int64).contiguous()
         B, d = nodes.numel(), E1.shape[1]
         f = dict(dtype=torch.float32, device=dev)
