@@ -90,8 +90,156 @@ __global__ void col_block_scatter_kernel(const int64_t* __restrict__ rowptr,
   }
 }
 
+// Row order (hgd_spmm_row_order): a group of kOrdG lanes per row, kBlock / kOrdG rows per block.
+constexpr int kOrdG = 16;
+
+// key[r] = the smallest column of row r (its columns need not ascend), n_cols for an empty row.
+__global__ __launch_bounds__(kBlock) void row_min_key_kernel(const int64_t* __restrict__ rowptr,
+                                                             const int32_t* __restrict__ col,
+                                                             int64_t n_rows, int32_t n_cols,
+                                                             int32_t* __restrict__ key) {
+  const int l = threadIdx.x % kOrdG;
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * (kBlock / kOrdG) + threadIdx.x / kOrdG;
+  if (r >= n_rows) return;  // group-uniform
+  const int64_t b = rowptr[r], e = rowptr[r + 1];
+  int32_t m = n_cols;
+  for (int64_t i = b + l; i < e; i += kOrdG) m = min(m, col[i]);
+#pragma unroll
+  for (int w = kOrdG / 2; w >= 1; w >>= 1) m = min(m, __shfl_xor(m, w, kOrdG));
+  if (l == 0) key[r] = m;
+}
+
+// len[p] = length of the row at position p; len[n_rows] = 0 closes the scan.
+__global__ void row_order_len_kernel(const int64_t* __restrict__ rowptr,
+                                     const int32_t* __restrict__ order, int64_t n_rows,
+                                     int64_t* __restrict__ len) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p > n_rows) return;
+  int64_t n = 0;
+  if (p < n_rows) {
+    const int64_t r = order[p];
+    n = rowptr[r + 1] - rowptr[r];
+  }
+  len[p] = n;
+}
+
+// Copies row order[p] to position p: its columns, in their own order, and their source positions.
+__global__ __launch_bounds__(kBlock) void row_order_copy_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+    const int32_t* __restrict__ order, const int64_t* __restrict__ rowptr_o, int64_t n_rows,
+    int32_t* __restrict__ col_o, int32_t* __restrict__ perm) {
+  const int l = threadIdx.x % kOrdG;
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * (kBlock / kOrdG) + threadIdx.x / kOrdG;
+  if (p >= n_rows) return;
+  const int64_t r = order[p];
+  const int64_t src = rowptr[r], n = rowptr[r + 1] - src, dst = rowptr_o[p];
+  for (int64_t i = l; i < n; i += kOrdG) {
+    col_o[dst + i] = col[src + i];
+    perm[dst + i] = static_cast<int32_t>(src + i);
+  }
+}
+
+// workspace of hgd_spmm_row_order: keys, sorted keys, permuted lengths, then the sort's and the
+// scan's own (one after the other in the same tail)
+struct RowOrderWs {
+  size_t keys, keys_s, len, tail, total;
+};
+
+RowOrderWs row_order_ws(int64_t n_rows) {
+  RowOrderWs w{};
+  size_t scan = 0;
+  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan, static_cast<const int64_t*>(nullptr),
+                                       static_cast<int64_t*>(nullptr), n_rows + 1) != hipSuccess)
+    return w;
+  const size_t sort = hgd_sort_perm_workspace_size(n_rows);
+  if (sort == 0) return w;
+  const size_t k = align_up(static_cast<size_t>(n_rows) * sizeof(int32_t));
+  w.keys = 0;
+  w.keys_s = k;
+  w.len = 2 * k;
+  w.tail = w.len + align_up(static_cast<size_t>(n_rows + 1) * sizeof(int64_t));
+  w.total = w.tail + (sort > align_up(scan) ? sort : align_up(scan));
+  return w;
+}
+
 }  // namespace
 }  // namespace hgd
+
+extern "C" size_t hgd_spmm_row_order_workspace_size(int64_t n_rows) {
+  if (n_rows <= 0 || n_rows >= 0x7fffffffLL) return 0;
+  return hgd::row_order_ws(n_rows).total;
+}
+
+extern "C" hgd_status hgd_spmm_row_order(const int64_t* rowptr, const int32_t* col,
+                                         int64_t n_rows, int64_t n_cols, int32_t* order,
+                                         int64_t* rowptr_o, int32_t* col_o, int32_t* perm,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace hgd;
+  clear_error();
+  HGD_REQUIRE(n_rows >= 0 && n_cols >= 0, "hgd_spmm_row_order: negative sizes");
+  HGD_REQUIRE(n_rows < 0x7fffffffLL, "hgd_spmm_row_order: n_rows >= 2^31 - 1");
+  HGD_REQUIRE(n_cols < 0x7fffffffLL, "hgd_spmm_row_order: n_cols >= 2^31 - 1");
+  if (n_rows == 0) return HGD_OK;
+  HGD_REQUIRE(rowptr && order && rowptr_o, "hgd_spmm_row_order: null rowptr / order / rowptr_o");
+  const RowOrderWs w = row_order_ws(n_rows);
+  if (w.total == 0 || !workspace || workspace_bytes < w.total)
+    return fail(HGD_ERR_WORKSPACE, "hgd_spmm_row_order: workspace %zu < %zu", workspace_bytes,
+                w.total);
+  constexpr int kRowsPerBlock = kBlock / kOrdG;
+  const int64_t grid = (n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  HGD_REQUIRE(grid <= 0x7fffffffLL, "hgd_spmm_row_order: too many rows");
+  hipStream_t st = as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  int32_t* keys = reinterpret_cast<int32_t*>(ws + w.keys);
+  int32_t* keys_s = reinterpret_cast<int32_t*>(ws + w.keys_s);
+  int64_t* len = reinterpret_cast<int64_t*>(ws + w.len);
+  hipLaunchKernelGGL(row_min_key_kernel, dim3(grid), dim3(kBlock), 0, st, rowptr, col, n_rows,
+                     static_cast<int32_t>(n_cols), keys);
+  hgd_status s = check_launch("hgd_spmm_row_order keys");
+  if (s != HGD_OK) return s;
+  // stable: rows with the same smallest column stay in natural order
+  s = hgd_sort_perm(keys, n_rows, n_cols + 1, keys_s, order, ws + w.tail, workspace_bytes - w.tail,
+                    stream);
+  if (s != HGD_OK) return s;
+  hipLaunchKernelGGL(row_order_len_kernel, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, st, rowptr,
+                     order, n_rows, len);
+  s = check_launch("hgd_spmm_row_order lengths");
+  if (s != HGD_OK) return s;
+  size_t tail_bytes = workspace_bytes - w.tail;
+  HGD_HIP(hipcub::DeviceScan::ExclusiveSum(ws + w.tail, tail_bytes, len, rowptr_o, n_rows + 1, st));
+  hipLaunchKernelGGL(row_order_copy_kernel, dim3(grid), dim3(kBlock), 0, st, rowptr, col, order,
+                     rowptr_o, n_rows, col_o, perm);
+  return check_launch("hgd_spmm_row_order copy");
+}
+
+extern "C" int32_t hgd_spmm_row_order_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz,
+                                          int32_t d) {
+  if (n_rows <= 0 || n_src_rows <= 0 || nnz <= 0 || d <= 0) return 0;
+  // the table one pass gathers from (rows wider than 128 run as 64-column passes): one that fits
+  // the aggregate L2 (8 XCDs × 4 MiB) is served from it in any order
+  const double table = static_cast<double>(n_src_rows) * (d <= 128 ? d : 64) * 4.0;
+  if (table < 33554432.0) return 0;
+  // the order turns about one gather per row: nothing to gain on long rows
+  if (nnz > 32 * n_rows) return 0;
+  // between the two bounds it is on: at 10 M users × 1 M items × 100 M edges the ordered hop into
+  // users is 7–8 % faster at d = 32, 64 and 128 (scripts/bench_row_order.py)
+  return 1;
+}
+
+extern "C" hgd_status hgd_spmm_ordered(const int64_t* rowptr, const int32_t* col,
+                                       const float* val, const float* row_scale, int64_t n_rows,
+                                       int64_t n_src_rows, int64_t row_begin, int64_t row_end,
+                                       const float* X, int64_t ldx, float* Y, int64_t ldy,
+                                       int32_t d, int32_t epilogue, float slope,
+                                       const hgd_split_plan* plan, void* workspace,
+                                       size_t workspace_bytes, const int32_t* out_row,
+                                       void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(out_row || n_rows <= 0, "hgd_spmm_ordered: null out_row");
+  return hgd::spmm_launch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end, X,
+                        ldx, Y, ldy, d, epilogue, slope, nullptr, nullptr, 1.f, plan, workspace,
+                        workspace_bytes, stream, "hgd_spmm_ordered", nullptr, 0, out_row);
+}
 
 extern "C" hgd_status hgd_spmm(const int64_t* rowptr, const int32_t* col, const float* val,
                                const float* row_scale, int64_t n_rows, int64_t n_src_rows,

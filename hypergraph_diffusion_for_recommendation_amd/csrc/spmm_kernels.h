@@ -55,6 +55,10 @@ struct SpmmArgsT {
   // copy (hgd_spmm_col_blocks), whose rows of block k are a CSR of their own (rowptr =
   // blk_start + k·n_rows); with blk_accum the row adds s·Σ to the Y row the blocks before wrote
   int32_t blk_accum;
+  // ordered hop (hgd_spmm_ordered): the rows are walked in the order of hgd_spmm_row_order —
+  // position r indexes rowptr / row_scale (the ordered copies) and the row is written to Y row
+  // out_row[r]; NULL: Y row r
+  const int32_t* out_row;
 };
 using SpmmArgs = SpmmArgsT<>;
 
@@ -76,24 +80,26 @@ constexpr int kPolNtIndex = 2;   // col / val streams: non-temporal loads (read 
 constexpr int kPolNtGather = 4;  // gathered X rows: non-temporal loads
 constexpr int kPolPrefetch = 8;  // software-pipelined index batches (see gather_sum)
 
-// Scale, epilogue and store of one finished row r (all G lanes of the group call it together).
+// Scale, epilogue and store of one finished row r (all G lanes of the group call it together);
+// yr is its row of Y (r, or the ordered hop's out_row[r]).
 // With EX the hgd_row_epilogue runs in registers: the group holds the whole row (single column
 // pass, checked on the host), so the LayerNorm statistics are two group_sum butterflies.
 template <int G, int VEC, bool EX, bool NT_STORE, class TX = float, class TY = float>
-__device__ __forceinline__ void finish_row(const SpmmArgsT<TX, TY>& a, int64_t r, float s, int l,
-                                           int64_t coff, bool col_ok, float (&acc)[VEC]) {
+__device__ __forceinline__ void finish_row(const SpmmArgsT<TX, TY>& a, int64_t r, int64_t yr,
+                                           float s, int l, int64_t coff, bool col_ok,
+                                           float (&acc)[VEC]) {
   if constexpr (!EX) {
     if (a.blk_accum) {  // a later block of a column-blocked hop: Y = epi(s·Σ_block + Y)
       float prev[VEC];
       if (col_ok) {
-        load_vec<VEC>(a.Y + r * a.ldy + coff, prev);
+        load_vec<VEC>(a.Y + yr * a.ldy + coff, prev);
       } else {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) prev[i] = 0.f;
       }
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = epilogue(acc[i] * s + prev[i], a.epi, a.slope);
-      if (col_ok) store_vec<VEC, NT_STORE>(a.Y + r * a.ldy + coff, acc);
+      if (col_ok) store_vec<VEC, NT_STORE>(a.Y + yr * a.ldy + coff, acc);
       return;
     }
   }
@@ -143,7 +149,7 @@ __device__ __forceinline__ void finish_row(const SpmmArgsT<TX, TY>& a, int64_t r
       for (int i = 0; i < VEC; ++i) acc[i] = fmaf(e.res2_scale, rv[i], acc[i]);
     }
   }
-  if (col_ok) store_vec<VEC, NT_STORE>(a.Y + r * a.ldy + coff, acc);
+  if (col_ok) store_vec<VEC, NT_STORE>(a.Y + yr * a.ldy + coff, acc);
   if constexpr (EX) {
     const hgd_row_epilogue& e = a.ex;
     if (e.sum_out && col_ok) {
@@ -412,8 +418,10 @@ __device__ __forceinline__ void masked_or_plain_sum(const SpmmArgsT<TX, TY>& a, 
   gather_sum<G, VEC, U, HAS_VAL, POL, MASK>(a, e0, e1, l, col_ok, acc, col0);
 }
 
+// ORD: the ordered hop (a.out_row set), an instantiation of its own so that every other one is
+// the code it was
 template <int G, int VEC, int U, bool HAS_VAL, int POL, bool EX, bool MASK = false,
-          class TX = float, class TY = float>
+          class TX = float, class TY = float, bool ORD = false>
 __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgsT<TX, TY> a) {
   constexpr int GPB = kBlock / G;
   const int g = threadIdx.x / G;
@@ -453,9 +461,12 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgsT<TX, TY> a) {
   const int64_t e0 = a.rowptr[r];
   const int64_t e1 = a.rowptr[r + 1];
   if (a.heavy_threshold > 0 && e1 - e0 > a.heavy_threshold) return;  // split-plan row
+  int32_t orow = 0;  // the ordered hop's Y row: one load per row, issued ahead of the gathers
+  if constexpr (ORD) orow = a.out_row[r];
   masked_or_plain_sum<G, VEC, U, HAS_VAL, POL, MASK>(a, e0, e1, l, col_ok, acc, col0);
+  const int64_t yr = ORD ? static_cast<int64_t>(orow) : r;
   const float s = a.row_scale ? a.row_scale[r] : 1.f;
-  finish_row<G, VEC, EX, (POL & kPolNtStore) != 0>(a, r, s, l, coff, col_ok, acc);
+  finish_row<G, VEC, EX, (POL & kPolNtStore) != 0>(a, r, yr, s, l, coff, col_ok, acc);
 }
 
 // Segmented variant for short rows (hgd_split_plan.flags & HGD_PLAN_SEGMENTED): a group owns
@@ -495,7 +506,8 @@ __global__ __launch_bounds__(kBlock) void spmm_seg_kernel(SpmmArgsT<TX, TY> a) {
       y[i] = acc[i];
       acc[i] = 0.f;
     }
-    finish_row<G, VEC, EX, (POL & kPolNtStore) != 0>(a, r0 + cur, s, l, coff, col_ok, y);
+    finish_row<G, VEC, EX, (POL & kPolNtStore) != 0>(a, r0 + cur, r0 + cur, s, l, coff, col_ok,
+                                                     y);
     ++cur;
     const int64_t nb = __shfl(my_end, cur < nr ? cur : 0, G);
     next_b = cur < nr ? nb : INT64_MAX;
@@ -608,7 +620,7 @@ __global__ __launch_bounds__(kBlock) void spmm_fixup_kernel(SpmmArgsT<TX, TY> a)
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] += s_acc[k][l * VEC + i];
   const float s = a.row_scale ? a.row_scale[r] : 1.f;
-  finish_row<G, VEC, EX, false>(a, r, s, l, coff, col_ok, acc);
+  finish_row<G, VEC, EX, false>(a, r, r, s, l, coff, col_ok, acc);
 }
 
 }  // namespace hgd

@@ -55,6 +55,17 @@ void launch_kernel(const SpmmArgsT<TX, TY>& a, const SpmmLaunch& L, bool seg, in
       return;
     }
   }
+  if constexpr (kF32<TX, TY> && !EX) {
+    if (a.out_row) {  // the ordered hop (no mask, no segmented walk: spmm_launch)
+      if (L.has_val)
+        hipLaunchKernelGGL((spmm_kernel<G, VEC, U, true, POL, false, false, TX, TY, true>),
+                           dim3(blocks), dim3(kBlock), 0, L.st, a);
+      else
+        hipLaunchKernelGGL((spmm_kernel<G, VEC, U, false, POL, false, false, TX, TY, true>),
+                           dim3(blocks), dim3(kBlock), 0, L.st, a);
+      return;
+    }
+  }
   if (L.has_val)
     hipLaunchKernelGGL((spmm_kernel<G, VEC, U, true, POL, EX, false, TX, TY>), dim3(blocks),
                        dim3(kBlock), 0, L.st, a);
@@ -341,15 +352,31 @@ hgd_status spmm_launch(const int64_t* rowptr, const int32_t* col, const float* v
                        const hgd_row_epilogue* ex, const uint8_t* mask, float keep,
                        const hgd_split_plan* plan, void* workspace, size_t workspace_bytes,
                        void* stream, const char* fn, const int64_t* blk_seg = nullptr,
-                       int32_t n_blk = 0) {
+                       int32_t n_blk = 0, const int32_t* out_row = nullptr) {
   bool run = false;
   hgd_status s = spmm_check_args(fn, rowptr, n_rows, n_src_rows, row_begin, row_end, X, ldx, Y,
                                  ldy, d, epilogue, slope, ex, &run);
-  if (s != HGD_OK || !run) return s;
+  if (s != HGD_OK) return s;
+  if (out_row) {
+    // the ordered hop (hgd_spmm_ordered) is the row kernel over every row: a split plan's chunks
+    // and fix-up and the segmented walk index Y by position, a row range is one of positions, and
+    // the fused epilogue's side tables and the blocked hop's passes are indexed by row
+    if ((plan && plan->threshold > 0 && plan->n_heavy > 0) ||
+        (plan && (plan->flags & HGD_PLAN_SEGMENTED)))
+      return fail(HGD_ERR_UNSUPPORTED, "%s: no split rows or segmented walk with a row order", fn);
+    if (mask || ex || blk_seg)
+      return fail(HGD_ERR_UNSUPPORTED,
+                  "%s: no mask, fused row epilogue or source blocks with a row order", fn);
+    if (row_begin != 0 || row_end != n_rows)
+      return fail(HGD_ERR_UNSUPPORTED, "%s: a row order covers all rows, got [%lld,%lld) of %lld",
+                  fn, (long long)row_begin, (long long)row_end, (long long)n_rows);
+  }
+  if (!run) return s;
   SpmmArgsT<TX, TY> a{};
   s = spmm_fill_args(a, fn, rowptr, col, val, row_scale, row_begin, row_end, X, ldx, Y, ldy, d,
                      epilogue, slope, ex, mask, keep, plan, workspace, workspace_bytes);
   if (s != HGD_OK) return s;
+  a.out_row = out_row;
   SpmmPassPlan p;
   s = spmm_pass_plan(fn, X, ldx, sizeof(TX), Y, ldy, sizeof(TY), d, ex, blk_seg != nullptr, &p);
   if (s != HGD_OK) return s;

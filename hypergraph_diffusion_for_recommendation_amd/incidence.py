@@ -88,6 +88,8 @@ class CSR:
         self.cols_ascending = False
         self._col_blocks: Dict[int, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
         self._blk_vals: Dict[Tuple[int, int], tuple] = {}
+        self._row_order: Optional[Tuple[torch.Tensor, ...]] = None
+        self._ord_vals: Dict[Tuple[int, int], tuple] = {}
         self._plan_arrays = ()
         self.plan = nat.SplitPlan()
         self.plan.threshold = 0
@@ -187,19 +189,47 @@ class CSR:
         every hop; the last 8 are kept."""
         if val is None:
             return None
-        try:
-            version = val._version
-        except RuntimeError:  # an inference tensor tracks no version: gathered every call
-            return _gather32(val, self.col_blocks(n_blocks)[2])
-        key = (n_blocks, id(val))
-        hit = self._blk_vals.get(key)
-        if hit is not None and hit[0]() is val and hit[1] == version:
-            return hit[2]
-        bval = _gather32(val, self.col_blocks(n_blocks)[2])
-        if len(self._blk_vals) >= 8:
-            self._blk_vals.pop(next(iter(self._blk_vals)))
-        self._blk_vals[key] = (weakref.ref(val), version, bval)
-        return bval
+        return _gather32_cached(self._blk_vals, n_blocks, val, self.col_blocks(n_blocks)[2])
+
+    def row_order(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The rows in ascending order of their smallest column, for the ordered hop
+        (hgd_spmm_row_order): ``(order [n_rows] int32, rowptr_o [n_rows+1] int64, col_o [nnz]
+        int32, perm [nnz] int32)`` — position p processes row ``order[p]``, whose nonzeros are
+        ``[rowptr_o[p], rowptr_o[p+1])`` of ``col_o`` in their own order; ``perm`` is the source
+        position of every entry. Built once, on the current stream."""
+        got = self._row_order
+        if got is None:
+            dev = self.device
+            lib = nat.load()
+            order = torch.empty(self.n_rows, dtype=torch.int32, device=dev)
+            rowptr_o = torch.empty(self.n_rows + 1, dtype=torch.int64, device=dev)
+            col_o = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+            perm = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+            if self.n_rows:
+                ws = _ws(lib.hgd_spmm_row_order_workspace_size(self.n_rows), dev)
+                nat.check(lib.hgd_spmm_row_order(
+                    self.rowptr.data_ptr(), self.col.data_ptr() if self.nnz else None,
+                    self.n_rows, self.n_cols, order.data_ptr(), rowptr_o.data_ptr(),
+                    col_o.data_ptr() if self.nnz else None, perm.data_ptr() if self.nnz else None,
+                    ws.data_ptr(), ws.numel(), _stream(dev)), "hgd_spmm_row_order")
+            else:
+                rowptr_o.zero_()
+            got = self._row_order = (order, rowptr_o, col_o, perm)
+        return got
+
+    def ordered_values(self, val: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """``val`` (per-nonzero weights) in the entry order of :meth:`row_order`; cached like
+        :meth:`blocked_values`."""
+        if val is None:
+            return None
+        return _gather32_cached(self._ord_vals, 0, val, self.row_order()[3])
+
+    def ordered_scale(self, row_scale: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """``row_scale`` (one per row) in the processing order of :meth:`row_order`; cached
+        like :meth:`blocked_values`."""
+        if row_scale is None:
+            return None
+        return _gather32_cached(self._ord_vals, 1, row_scale, self.row_order()[0])
 
     @property
     def n_heavy(self) -> int:
@@ -239,6 +269,28 @@ def spmm_blocks(csr: CSR, d: int) -> int:
         return p if p > 1 else 0
     # the library's size rule (hgd_spmm_blocks_for), shared with the native incidence objects
     return int(nat.load().hgd_spmm_blocks_for(csr.n_cols, int(d)))
+
+
+def spmm_row_order(csr: CSR, d: int) -> bool:
+    """Whether the plain fp32 hop over ``csr`` at width ``d`` walks its rows in ascending order
+    of their smallest column (hgd_spmm_ordered over :meth:`CSR.row_order`).
+
+    A short row's gathers are spread over the whole source table, so an XCD's 4 MiB of L2 sees
+    almost no reuse; rows that share their smallest column processed next to each other make
+    the first gather of most rows an L2 hit. Nothing inside a row changes: the sums are bitwise
+    those of hgd_spmm. The price is Y rows written in permuted order and one 4-byte row id per
+    row. The size rule is the library's (hgd_spmm_row_order_for).
+
+    Only without split rows or the segmented walk. ``HGD_SPMM_ROW_ORDER``: ``0`` off, ``1`` on
+    wherever it applies, unset (or ``auto``) = the size rule."""
+    if csr.n_heavy or csr.segmented or csr.nnz == 0:
+        return False
+    env = os.environ.get("HGD_SPMM_ROW_ORDER", "")
+    if env not in ("", "auto"):
+        if env not in ("0", "1"):
+            raise ValueError(f"HGD_SPMM_ROW_ORDER must be 0 or 1, got {env!r}")
+        return env == "1"
+    return bool(nat.load().hgd_spmm_row_order_for(csr.n_rows, csr.n_cols, csr.nnz, int(d)))
 
 
 # element types of the hop's table and output -> HGD_DT_* (hgd_spmm_dt)
@@ -317,7 +369,17 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     sp, n, m, rb, re_ = nat.ptr(row_scale), csr.n_rows, csr.n_cols, int(row_begin), int(row_end)
     xp, ldx, yp, ldy = X.data_ptr(), X.stride(0), out.data_ptr(), out.stride(0)
     wp, st = nat.ptr(ws), _stream(X.device)
-    if dt and mask is not None:
+    # the plain fp32 hop over the whole row range may walk its rows in min-column order
+    ordered = (not dt and mask is None and ex is None and not blocks and rb == 0 and re_ == n
+               and spmm_row_order(csr, d))
+    if ordered:
+        order, rowptr_o, col_o, _ = csr.row_order()
+        nat.check(lib.hgd_spmm_ordered(
+            rowptr_o.data_ptr(), col_o.data_ptr(), nat.ptr(csr.ordered_values(val)),
+            nat.ptr(csr.ordered_scale(row_scale)), n, m, rb, re_, xp, ldx, yp, ldy, d,
+            int(epilogue), float(slope), plan_ptr, wp, wsb, order.data_ptr(), st),
+            "hgd_spmm_ordered")
+    elif dt and mask is not None:
         nat.check(lib.hgd_spmm_masked_dt(
             rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, _HOP_DTYPES[X.dtype], ldx, yp,
             _HOP_DTYPES[y_dtype], ldy, d, int(epilogue), float(slope), plan_ptr, wp, wsb, st),
@@ -354,11 +416,11 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
 
         def nbytes(csr=csr, rb=rb, re_=re_, full=full, d=d, hv=val is not None,
                    hs=row_scale is not None, blocks=blocks, xb=X.element_size(),
-                   yb=out.element_size()):
+                   yb=out.element_size(), ordered=ordered):
             nnz = csr.nnz if full else int(csr.rowptr[re_].item() - csr.rowptr[rb].item())
             return (profiling.hop_bytes(nnz, re_ - rb, d, x_bytes=xb, y_bytes=yb),
                     profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, blocks, x_bytes=xb,
-                                         y_bytes=yb))
+                                         y_bytes=yb, ordered=ordered))
 
         timer.end(t0, nbytes)
     return out
@@ -804,6 +866,26 @@ def _gather32(src: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
     if n:
         nat.check(nat.load().hgd_gather32(src.data_ptr(), perm.data_ptr(), n, out.data_ptr(),
                                           _stream(src.device)), "hgd_gather32")
+    return out
+
+
+def _gather32_cached(cache: dict, kind: int, src: torch.Tensor,
+                     perm: torch.Tensor) -> torch.Tensor:
+    """``_gather32(src, perm)`` cached in ``cache`` under (kind, id(src)) while ``src`` is alive
+    and unmodified (its version counter), e.g. the cached ``Incidence.edge_values`` a training
+    step passes to every hop; the last 8 are kept."""
+    try:
+        version = src._version
+    except RuntimeError:  # an inference tensor tracks no version: gathered every call
+        return _gather32(src, perm)
+    key = (kind, id(src))
+    hit = cache.get(key)
+    if hit is not None and hit[0]() is src and hit[1] == version:
+        return hit[2]
+    out = _gather32(src, perm)
+    if len(cache) >= 8:
+        cache.pop(next(iter(cache)))
+    cache[key] = (weakref.ref(src), version, out)
     return out
 
 

@@ -36,11 +36,14 @@ def hop_bytes(nnz: int, rows: int, d: int, weighted: bool = False, x_bytes: int 
 
 
 def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
-               blocks: int = 0, x_bytes: int = 4, y_bytes: int = 4) -> int:
+               blocks: int = 0, x_bytes: int = 4, y_bytes: int = 4, ordered: bool = False) -> int:
     """Bytes the hgd_spmm launch streams at minimum as implemented (int64 rowptr, weights).
     A source-blocked hop (hgd_spmm_blocked, ``blocks`` = P > 1) reads the [R × (P+1)] int64
     block starts instead of the rowptr, writes every Y row P times, reads it back P−1 times and
-    applies the row scale in every pass."""
+    applies the row scale in every pass. An ordered hop (hgd_spmm_ordered) also reads the int32
+    output row of every row."""
+    if ordered:
+        return impl_bytes(nnz, rows, d, has_val, has_scale, 0, x_bytes, y_bytes) + rows * 4
     if blocks > 1:
         return (nnz * (4 + (4 if has_val else 0) + x_bytes * d)
                 + rows * (y_bytes * d * (2 * blocks - 1) + (4 * blocks if has_scale else 0))

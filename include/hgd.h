@@ -261,6 +261,42 @@ hgd_status hgd_spmm_blocked(const int64_t* blk_start, const int32_t* blk_col,
                             const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d,
                             int32_t epilogue, float slope, int32_t n_blocks, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The same hop (hgd_spmm, every row, fp32) with the rows WALKED in ascending order of their
+ * smallest column, so that rows sharing a source row run next to each other and find it in L2.
+ * Replaces the same call sites as hgd_spmm (torch.sparse.mm(adj, X), model/graph/HCCF.py:199).
+ * Nothing inside a row changes — the same fmaf chain in edge order — so Y is bitwise hgd_spmm's.
+ *
+ * hgd_spmm_row_order builds the order of a structure (its rows' columns in any order), once:
+ *   order:    int32 [n_rows], the row processed at position p; ascending smallest column (an
+ *             empty row counts as n_cols), ties in natural row order (hgd_sort_perm, stable)
+ *   rowptr_o: int64 [n_rows+1], the row pointers in processing order
+ *   col_o:    int32 [nnz], the columns of the rows in that order, each row's in its own order
+ *   perm:     int32 [nnz], the source position of every entry — gather per-nonzero weights
+ *             through it and per-row scales through `order` (hgd_gather32); nnz < 2^31
+ * No atomics, stream-ordered, no host synchronisation. Workspace:
+ * hgd_spmm_row_order_workspace_size.
+ *
+ * hgd_spmm_ordered: hgd_spmm's arguments with rowptr / col / val / row_scale the ORDERED copies
+ * and out_row = order: position p writes Y row out_row[p]. HGD_ERR_UNSUPPORTED for a plan with
+ * split rows or HGD_PLAN_SEGMENTED and for a row range other than [0, n_rows) (and, inside the
+ * library, with a mask, a fused row epilogue or source blocks).
+ * ---------------------------------------------------------------------------------------- */
+/* The size rule both hosts use: 1 when a hop of nnz nonzeros over n_rows rows
+ * gathering n_src_rows rows at width d should run ordered, else 0. */
+int32_t hgd_spmm_row_order_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz, int32_t d);
+size_t hgd_spmm_row_order_workspace_size(int64_t n_rows);
+hgd_status hgd_spmm_row_order(const int64_t* rowptr, const int32_t* col, int64_t n_rows,
+                              int64_t n_cols, int32_t* order, int64_t* rowptr_o, int32_t* col_o,
+                              int32_t* perm, void* workspace, size_t workspace_bytes,
+                              void* stream);
+hgd_status hgd_spmm_ordered(const int64_t* rowptr, const int32_t* col, const float* val,
+                            const float* row_scale, int64_t n_rows, int64_t n_src_rows,
+                            int64_t row_begin, int64_t row_end, const float* X, int64_t ldx,
+                            float* Y, int64_t ldy, int32_t d, int32_t epilogue, float slope,
+                            const hgd_split_plan* plan, void* workspace, size_t workspace_bytes,
+                            const int32_t* out_row, void* stream);
+
 /* The same hop over the EDGE-DROPPED matrix of SpAdjDropEdge (model/graph/HCCF.py:213-226:
  * mask = floor(rand + keepRate), idxs[:, mask], vals[mask] / keepRate) without building it: the
  * structure is the parent's, `mask` (uint8, this orientation's edge order; for the CSC of the
