@@ -235,10 +235,12 @@ extern "C" hgd_status hgd_spmm_ordered(const int64_t* rowptr, const int32_t* col
                                        size_t workspace_bytes, const int32_t* out_row,
                                        void* stream) {
   hgd::clear_error();
-  HGD_REQUIRE(out_row || n_rows <= 0, "hgd_spmm_ordered: null out_row");
-  return hgd::spmm_launch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end, X,
-                        ldx, Y, ldy, d, epilogue, slope, nullptr, nullptr, 1.f, plan, workspace,
-                        workspace_bytes, stream, "hgd_spmm_ordered", nullptr, 0, out_row);
+  hgd::SpmmRequest r{"hgd_spmm_ordered", rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin,
+                     row_end, X, ldx, Y, ldy, d, epilogue, slope, plan, workspace, workspace_bytes,
+                     stream};
+  r.ordered = true;
+  r.out_row = out_row;
+  return hgd::spmm_launch<float, float>(r);
 }
 
 extern "C" hgd_status hgd_spmm(const int64_t* rowptr, const int32_t* col, const float* val,
@@ -248,9 +250,10 @@ extern "C" hgd_status hgd_spmm(const int64_t* rowptr, const int32_t* col, const 
                                const hgd_split_plan* plan, void* workspace,
                                size_t workspace_bytes, void* stream) {
   hgd::clear_error();
-  return hgd::spmm_launch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end, X,
-                        ldx, Y, ldy, d, epilogue, slope, nullptr, nullptr, 1.f, plan, workspace,
-                        workspace_bytes, stream, "hgd_spmm");
+  hgd::SpmmRequest r{"hgd_spmm", rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin,
+                     row_end, X, ldx, Y, ldy, d, epilogue, slope, plan, workspace, workspace_bytes,
+                     stream};
+  return hgd::spmm_launch<float, float>(r);
 }
 
 extern "C" int32_t hgd_spmm_blocks_for(int64_t n_src_rows, int32_t d) {
@@ -315,12 +318,13 @@ extern "C" hgd_status hgd_spmm_blocked(const int64_t* blk_start, const int32_t* 
                                        int64_t ldy, int32_t d, int32_t epilogue, float slope,
                                        int32_t n_blocks, void* stream) {
   hgd::clear_error();
-  HGD_REQUIRE(n_blocks >= 1 && n_blocks <= 64, "hgd_spmm_blocked: blocks must be 1..64");
-  HGD_REQUIRE(row_end <= row_begin || blk_start, "hgd_spmm_blocked: null blk_start");
-  // spmm_launch's rowptr argument is only checked for NULL on this path
-  return hgd::spmm_launch(blk_start, blk_col, blk_val, row_scale, n_rows, n_src_rows, row_begin,
-                        row_end, X, ldx, Y, ldy, d, epilogue, slope, nullptr, nullptr, 1.f,
-                        nullptr, nullptr, 0, stream, "hgd_spmm_blocked", blk_start, n_blocks);
+  hgd::SpmmRequest r{"hgd_spmm_blocked", nullptr, blk_col, blk_val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, epilogue, slope};
+  r.blocked = true;
+  r.blk_start = blk_start;
+  r.n_blk = n_blocks;
+  r.stream = stream;
+  return hgd::spmm_launch<float, float>(r);
 }
 
 extern "C" hgd_status hgd_spmm_fused(const int64_t* rowptr, const int32_t* col, const float* val,
@@ -331,9 +335,11 @@ extern "C" hgd_status hgd_spmm_fused(const int64_t* rowptr, const int32_t* col, 
                                      void* workspace, size_t workspace_bytes, void* stream) {
   hgd::clear_error();
   HGD_REQUIRE(epi != nullptr, "hgd_spmm_fused: null epilogue descriptor");
-  return hgd::spmm_launch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end, X,
-                        ldx, Y, ldy, d, epi->act, epi->slope, epi, nullptr, 1.f, plan, workspace,
-                        workspace_bytes, stream, "hgd_spmm_fused");
+  hgd::SpmmRequest r{"hgd_spmm_fused", rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin,
+                     row_end, X, ldx, Y, ldy, d, epi->act, epi->slope, plan, workspace,
+                     workspace_bytes, stream};
+  r.ex = epi;
+  return hgd::spmm_launch<float, float>(r);
 }
 
 extern "C" hgd_status hgd_spmm_masked(const int64_t* rowptr, const int32_t* col, const float* val,
@@ -344,11 +350,13 @@ extern "C" hgd_status hgd_spmm_masked(const int64_t* rowptr, const int32_t* col,
                                       const hgd_split_plan* plan, void* workspace,
                                       size_t workspace_bytes, void* stream) {
   hgd::clear_error();
-  HGD_REQUIRE(keep > 0.f, "hgd_spmm_masked: keep must be > 0 (got %g)", (double)keep);
-  HGD_REQUIRE(mask || row_end == row_begin, "hgd_spmm_masked: null mask");
-  return hgd::spmm_launch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end, X,
-                        ldx, Y, ldy, d, epilogue, slope, nullptr, mask, keep, plan, workspace,
-                        workspace_bytes, stream, "hgd_spmm_masked");
+  hgd::SpmmRequest r{"hgd_spmm_masked", rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin,
+                     row_end, X, ldx, Y, ldy, d, epilogue, slope, plan, workspace, workspace_bytes,
+                     stream};
+  r.masked = true;
+  r.mask = mask;
+  r.keep = keep;
+  return hgd::spmm_launch<float, float>(r);
 }
 
 extern "C" hgd_status hgd_spmm_masked_fused(const int64_t* rowptr, const int32_t* col,
@@ -362,9 +370,12 @@ extern "C" hgd_status hgd_spmm_masked_fused(const int64_t* rowptr, const int32_t
                                             size_t workspace_bytes, void* stream) {
   hgd::clear_error();
   HGD_REQUIRE(epi != nullptr, "hgd_spmm_masked_fused: null epilogue descriptor");
-  HGD_REQUIRE(keep > 0.f, "hgd_spmm_masked_fused: keep must be > 0 (got %g)", (double)keep);
-  HGD_REQUIRE(mask || row_end == row_begin, "hgd_spmm_masked_fused: null mask");
-  return hgd::spmm_launch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end, X,
-                        ldx, Y, ldy, d, epi->act, epi->slope, epi, mask, keep, plan, workspace,
-                        workspace_bytes, stream, "hgd_spmm_masked_fused");
+  hgd::SpmmRequest r{"hgd_spmm_masked_fused", rowptr, col, val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, epi->act, epi->slope, plan, workspace,
+                     workspace_bytes, stream};
+  r.ex = epi;
+  r.masked = true;
+  r.mask = mask;
+  r.keep = keep;
+  return hgd::spmm_launch<float, float>(r);
 }

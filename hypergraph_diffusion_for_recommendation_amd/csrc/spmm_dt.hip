@@ -25,22 +25,11 @@
 namespace hgd {
 namespace {
 
-hgd_status spmm_dt_dispatch(const int64_t* rowptr, const int32_t* col, const float* val,
-                            const float* row_scale, int64_t n_rows, int64_t n_src_rows,
-                            int64_t row_begin, int64_t row_end, const void* X, int32_t x_dtype,
-                            int64_t ldx, void* Y, int32_t y_dtype, int64_t ldy, int32_t d,
-                            int32_t epilogue, float slope, const uint8_t* mask, float keep,
-                            const hgd_split_plan* plan, void* workspace, size_t workspace_bytes,
-                            void* stream, const char* fn) {
-  auto hop = [&](auto* x, auto* y) {
-    return spmm_launch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end, x, ldx,
-                       y, ldy, d, epilogue, slope, nullptr, mask, keep, plan, workspace,
-                       workspace_bytes, stream, fn);
-  };
+hgd_status spmm_dt_dispatch(const SpmmRequest& r, int32_t x_dtype, int32_t y_dtype) {
   const bool xb = x_dtype == HGD_DT_BF16, yb = y_dtype == HGD_DT_BF16;
-  if (xb && yb) return hop(static_cast<const bf16*>(X), static_cast<bf16*>(Y));
-  if (xb) return hop(static_cast<const bf16*>(X), static_cast<float*>(Y));
-  return hop(static_cast<const float*>(X), static_cast<bf16*>(Y));
+  if (xb && yb) return spmm_launch<bf16, bf16>(r);
+  if (xb) return spmm_launch<bf16, float>(r);
+  return spmm_launch<float, bf16>(r);
 }
 
 bool dtype_ok(int32_t dt) { return dt == HGD_DT_F32 || dt == HGD_DT_BF16; }
@@ -63,10 +52,10 @@ extern "C" hgd_status hgd_spmm_dt(const int64_t* rowptr, const int32_t* col, con
     return hgd_spmm(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end,
                     static_cast<const float*>(X), ldx, static_cast<float*>(Y), ldy, d, epilogue,
                     slope, plan, workspace, workspace_bytes, stream);
-  return hgd::spmm_dt_dispatch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin,
-                               row_end, X, x_dtype, ldx, Y, y_dtype, ldy, d, epilogue, slope,
-                               nullptr, 1.f, plan, workspace, workspace_bytes, stream,
-                               "hgd_spmm_dt");
+  hgd::SpmmRequest r{"hgd_spmm_dt", rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin,
+                     row_end, X, ldx, Y, ldy, d, epilogue, slope, plan, workspace, workspace_bytes,
+                     stream};
+  return hgd::spmm_dt_dispatch(r, x_dtype, y_dtype);
 }
 
 extern "C" hgd_status hgd_spmm_masked_dt(const int64_t* rowptr, const int32_t* col,
@@ -86,10 +75,11 @@ extern "C" hgd_status hgd_spmm_masked_dt(const int64_t* rowptr, const int32_t* c
     return hgd_spmm_masked(rowptr, col, val, mask, keep, row_scale, n_rows, n_src_rows, row_begin,
                            row_end, static_cast<const float*>(X), ldx, static_cast<float*>(Y),
                            ldy, d, epilogue, slope, plan, workspace, workspace_bytes, stream);
-  HGD_REQUIRE(keep > 0.f, "hgd_spmm_masked_dt: keep must be > 0 (got %g)", (double)keep);
-  HGD_REQUIRE(mask || row_end == row_begin, "hgd_spmm_masked_dt: null mask");
-  return hgd::spmm_dt_dispatch(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin,
-                               row_end, X, x_dtype, ldx, Y, y_dtype, ldy, d, epilogue, slope, mask,
-                               keep, plan, workspace, workspace_bytes, stream,
-                               "hgd_spmm_masked_dt");
+  hgd::SpmmRequest r{"hgd_spmm_masked_dt", rowptr, col, val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, epilogue, slope, plan, workspace,
+                     workspace_bytes, stream};
+  r.masked = true;
+  r.mask = mask;
+  r.keep = keep;
+  return hgd::spmm_dt_dispatch(r, x_dtype, y_dtype);
 }

@@ -18,11 +18,44 @@ static_assert(SpmmTuning{}.policy == kDefaultPolicy && SpmmTuning{}.unroll == 8)
 template <class TX, class TY>
 constexpr bool kF32 = std::is_same_v<TX, float> && std::is_same_v<TY, float>;
 
-// What a launch needs besides the argument block; fn is the entry point the caller called.
-struct SpmmLaunch {
-  const char* fn;
-  bool has_val;
-  hipStream_t st;
+// One hop as its extern "C" entry point describes it: the entry point fills a request and calls
+// spmm_launch (or spmm_dt.hip's dtype switch), and everything below reads the request. The
+// members down to stream are hgd_spmm's arguments in its order, so an entry point initialises
+// them from its own in one list; what only some entry points take is named where it is set.
+struct SpmmRequest {
+  const char* fn;  // the entry point the caller called: the prefix of every error message
+  // the structure: CSR of n_rows rows over n_src_rows source rows (val / row_scale: or NULL)
+  const int64_t* rowptr;  // NULL for a blocked hop, whose blocks bring their own (blk_start)
+  const int32_t* col;
+  const float* val;
+  const float* row_scale;
+  int64_t n_rows, n_src_rows;
+  int64_t row_begin, row_end;  // the rows [row_begin, row_end) of Y this call writes
+  // the gathered table and the output; spmm_launch's TX / TY say what they point to
+  const void* X;
+  int64_t ldx;
+  void* Y;
+  int64_t ldy;
+  int32_t d;
+  int32_t epilogue;  // HGD_EPI_*
+  float slope;
+  const hgd_split_plan* plan = nullptr;
+  void* workspace = nullptr;  // of the plan's split rows
+  size_t workspace_bytes = 0;
+  void* stream = nullptr;
+  const hgd_row_epilogue* ex = nullptr;  // the fused row epilogue
+  // the edge-dropped view (masked: the entry point takes one)
+  bool masked = false;
+  const uint8_t* mask = nullptr;
+  float keep = 1.f;
+  // the source blocks (hgd_spmm_blocked): the block-major blk_start, n_blk of them over n_rows
+  // rows each, with col / val the block-major arrays
+  bool blocked = false;
+  const int64_t* blk_start = nullptr;
+  int32_t n_blk = 0;
+  // the row order (hgd_spmm_ordered): position p is written to Y row out_row[p]
+  bool ordered = false;
+  const int32_t* out_row = nullptr;
 };
 
 inline hgd_status check_launch(const char* fn, const char* what) {
@@ -31,51 +64,32 @@ inline hgd_status check_launch(const char* fn, const char* what) {
   return HGD_OK;
 }
 
-template <int G, int VEC, int U, int POL, bool EX, class TX, class TY>
-void launch_kernel(const SpmmArgsT<TX, TY>& a, const SpmmLaunch& L, bool seg, int64_t blocks) {
+// The kernel of one launch: the masked, the segmented, the ordered or the plain row kernel.
+template <bool HAS_VAL, int G, int VEC, int U, int POL, bool EX, class TX, class TY>
+auto pick_kernel(const SpmmArgsT<TX, TY>& a, bool seg) {
   if constexpr (POL == kDefaultPolicy && U == 8) {
-    if (a.mask) {  // masked (edge-dropped view) hop: the row kernel only
-      if (L.has_val)
-        hipLaunchKernelGGL((spmm_kernel<G, VEC, U, true, POL, EX, true, TX, TY>), dim3(blocks),
-                           dim3(kBlock), 0, L.st, a);
-      else
-        hipLaunchKernelGGL((spmm_kernel<G, VEC, U, false, POL, EX, true, TX, TY>), dim3(blocks),
-                           dim3(kBlock), 0, L.st, a);
-      return;
-    }
+    // masked (edge-dropped view) hop: the row kernel only
+    if (a.mask) return spmm_kernel<G, VEC, U, HAS_VAL, POL, EX, true, TX, TY>;
   }
   if constexpr (G >= 8) {
-    if (seg) {
-      if (L.has_val)
-        hipLaunchKernelGGL((spmm_seg_kernel<G, VEC, U, true, POL, EX, TX, TY>), dim3(blocks),
-                           dim3(kBlock), 0, L.st, a);
-      else
-        hipLaunchKernelGGL((spmm_seg_kernel<G, VEC, U, false, POL, EX, TX, TY>), dim3(blocks),
-                           dim3(kBlock), 0, L.st, a);
-      return;
-    }
+    if (seg) return spmm_seg_kernel<G, VEC, U, HAS_VAL, POL, EX, TX, TY>;
   }
   if constexpr (kF32<TX, TY> && !EX) {
-    if (a.out_row) {  // the ordered hop (no mask, no segmented walk: spmm_launch)
-      if (L.has_val)
-        hipLaunchKernelGGL((spmm_kernel<G, VEC, U, true, POL, false, false, TX, TY, true>),
-                           dim3(blocks), dim3(kBlock), 0, L.st, a);
-      else
-        hipLaunchKernelGGL((spmm_kernel<G, VEC, U, false, POL, false, false, TX, TY, true>),
-                           dim3(blocks), dim3(kBlock), 0, L.st, a);
-      return;
-    }
+    // the ordered hop (no mask, no segmented walk: spmm_check_args)
+    if (a.out_row) return spmm_kernel<G, VEC, U, HAS_VAL, POL, false, false, TX, TY, true>;
   }
-  if (L.has_val)
-    hipLaunchKernelGGL((spmm_kernel<G, VEC, U, true, POL, EX, false, TX, TY>), dim3(blocks),
-                       dim3(kBlock), 0, L.st, a);
-  else
-    hipLaunchKernelGGL((spmm_kernel<G, VEC, U, false, POL, EX, false, TX, TY>), dim3(blocks),
-                       dim3(kBlock), 0, L.st, a);
+  return spmm_kernel<G, VEC, U, HAS_VAL, POL, EX, false, TX, TY>;
+}
+
+template <int G, int VEC, int U, int POL, bool EX, class TX, class TY>
+void launch_kernel(const SpmmArgsT<TX, TY>& a, const SpmmRequest& r, bool seg, int64_t blocks) {
+  auto kernel = r.val ? pick_kernel<true, G, VEC, U, POL, EX>(a, seg)
+                      : pick_kernel<false, G, VEC, U, POL, EX>(a, seg);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, as_stream(r.stream), a);
 }
 
 template <int G, int VEC, bool EX, class TX, class TY>
-void launch_tuned(const SpmmArgsT<TX, TY>& a, const SpmmLaunch& L, bool seg, int64_t blocks) {
+void launch_tuned(const SpmmArgsT<TX, TY>& a, const SpmmRequest& r, bool seg, int64_t blocks) {
   if constexpr (kF32<TX, TY> && G == 16 && VEC == 4 && !EX) {
     // the fp32 d = 64 path without a mask carries the tuning matrix (unroll × {plain, nt-store,
     // prefetch, both, prefetch + nt-index, prefetch + nt-index + nt-store})
@@ -83,12 +97,12 @@ void launch_tuned(const SpmmArgsT<TX, TY>& a, const SpmmLaunch& L, bool seg, int
       const SpmmTuning& t = spmm_tuning();
 #define HGD_POL_CASES(U)                                                                  \
       switch (t.policy) {                                                                 \
-        case 0: return launch_kernel<G, VEC, U, 0, false>(a, L, seg, blocks);             \
-        case 1: return launch_kernel<G, VEC, U, 1, false>(a, L, seg, blocks);             \
-        case 9: return launch_kernel<G, VEC, U, 9, false>(a, L, seg, blocks);             \
-        case 10: return launch_kernel<G, VEC, U, 10, false>(a, L, seg, blocks);           \
-        case 11: return launch_kernel<G, VEC, U, 11, false>(a, L, seg, blocks);           \
-        default: return launch_kernel<G, VEC, U, 8, false>(a, L, seg, blocks);            \
+        case 0: return launch_kernel<G, VEC, U, 0, false>(a, r, seg, blocks);             \
+        case 1: return launch_kernel<G, VEC, U, 1, false>(a, r, seg, blocks);             \
+        case 9: return launch_kernel<G, VEC, U, 9, false>(a, r, seg, blocks);             \
+        case 10: return launch_kernel<G, VEC, U, 10, false>(a, r, seg, blocks);           \
+        case 11: return launch_kernel<G, VEC, U, 11, false>(a, r, seg, blocks);           \
+        default: return launch_kernel<G, VEC, U, 8, false>(a, r, seg, blocks);            \
       }
       if (t.unroll >= 16) { HGD_POL_CASES(16) }
       HGD_POL_CASES(8)
@@ -97,22 +111,22 @@ void launch_tuned(const SpmmArgsT<TX, TY>& a, const SpmmLaunch& L, bool seg, int
   }
   // everything else (a 16-bit side, another width, the fused epilogue, the masked hop): U = 8 with
   // the prefetch policy
-  launch_kernel<G, VEC, 8, kDefaultPolicy, EX>(a, L, seg, blocks);
+  launch_kernel<G, VEC, 8, kDefaultPolicy, EX>(a, r, seg, blocks);
 }
 
 // One column pass: the segmented walk, or the row kernel (split-row chunks first in the grid) and
 // the fix-up of the split rows.
 template <int G, int VEC, bool EX, class TX, class TY>
-hgd_status launch_g(SpmmArgsT<TX, TY> a, const SpmmLaunch& L) {
+hgd_status launch_g(SpmmArgsT<TX, TY> a, const SpmmRequest& r) {
   constexpr int GPB = kBlock / G;
   const int64_t rows = a.row_end - a.row_begin;
   if constexpr (G >= 8) {
     if (a.seg) {
       const int64_t sblocks = (rows + static_cast<int64_t>(GPB) * G - 1) / (GPB * G);
       if (sblocks <= 0) return HGD_OK;
-      if (sblocks > 0x7fffffffLL) return fail(HGD_ERR_UNSUPPORTED, "%s: grid too large", L.fn);
-      launch_tuned<G, VEC, EX>(a, L, true, sblocks);
-      return check_launch(L.fn, "segmented kernel");
+      if (sblocks > 0x7fffffffLL) return fail(HGD_ERR_UNSUPPORTED, "%s: grid too large", r.fn);
+      launch_tuned<G, VEC, EX>(a, r, true, sblocks);
+      return check_launch(r.fn, "segmented kernel");
     }
   }
   int64_t light_blocks = (rows + GPB - 1) / GPB;
@@ -120,56 +134,65 @@ hgd_status launch_g(SpmmArgsT<TX, TY> a, const SpmmLaunch& L) {
   if (a.n_pass > 1) light_blocks = (light_blocks + 7) / 8 * 8 * a.n_pass;  // (no split rows)
   const int64_t blocks = light_blocks + a.heavy_blocks;
   if (blocks > 0) {
-    if (blocks > 0x7fffffffLL) return fail(HGD_ERR_UNSUPPORTED, "%s: grid too large", L.fn);
-    launch_tuned<G, VEC, EX>(a, L, false, blocks);
-    hgd_status s = check_launch(L.fn, "kernel");
+    if (blocks > 0x7fffffffLL) return fail(HGD_ERR_UNSUPPORTED, "%s: grid too large", r.fn);
+    launch_tuned<G, VEC, EX>(a, r, false, blocks);
+    hgd_status s = check_launch(r.fn, "kernel");
     if (s != HGD_OK) return s;
   }
   if (a.n_heavy > 0) {
     if (a.n_heavy > 0x7fffffffLL)
-      return fail(HGD_ERR_UNSUPPORTED, "%s: too many split rows", L.fn);
+      return fail(HGD_ERR_UNSUPPORTED, "%s: too many split rows", r.fn);
     hipLaunchKernelGGL((spmm_fixup_kernel<G, VEC, EX, TX, TY>), dim3(a.n_heavy), dim3(kBlock), 0,
-                       L.st, a);
-    return check_launch(L.fn, "fixup");
+                       as_stream(r.stream), a);
+    return check_launch(r.fn, "fixup");
   }
   return HGD_OK;
 }
 
 template <int VEC, bool EX, class TX, class TY>
-hgd_status launch_vec(int G, const SpmmArgsT<TX, TY>& a, const SpmmLaunch& L) {
+hgd_status launch_vec(int G, const SpmmArgsT<TX, TY>& a, const SpmmRequest& r) {
   switch (G) {
-    case 1: return launch_g<1, VEC, EX>(a, L);
-    case 2: return launch_g<2, VEC, EX>(a, L);
-    case 4: return launch_g<4, VEC, EX>(a, L);
-    case 8: return launch_g<8, VEC, EX>(a, L);
-    case 16: return launch_g<16, VEC, EX>(a, L);
-    case 32: return launch_g<32, VEC, EX>(a, L);
+    case 1: return launch_g<1, VEC, EX>(a, r);
+    case 2: return launch_g<2, VEC, EX>(a, r);
+    case 4: return launch_g<4, VEC, EX>(a, r);
+    case 8: return launch_g<8, VEC, EX>(a, r);
+    case 16: return launch_g<16, VEC, EX>(a, r);
+    case 32: return launch_g<32, VEC, EX>(a, r);
     case 64:  // a pass of the 8-column path is at most 256 columns: 32 lanes
-      if constexpr (VEC != 8) return launch_g<64, VEC, EX>(a, L);
+      if constexpr (VEC != 8) return launch_g<64, VEC, EX>(a, r);
       [[fallthrough]];
-    default: return fail(HGD_ERR_UNSUPPORTED, "%s: unsupported group size %d", L.fn, G);
+    default: return fail(HGD_ERR_UNSUPPORTED, "%s: unsupported group size %d", r.fn, G);
   }
 }
 
-// The checks that do not depend on the element types. *run = false: an empty row range, nothing
-// to launch (the caller returns HGD_OK).
-inline hgd_status spmm_check_args(const char* fn, const void* rowptr, int64_t n_rows,
-                                  int64_t n_src_rows, int64_t row_begin, int64_t row_end,
-                                  const void* X, int64_t ldx, const void* Y, int64_t ldy,
-                                  int32_t d, int32_t epilogue, float slope,
-                                  const hgd_row_epilogue* ex, bool* run) {
-  *run = false;
+inline bool has_split_rows(const hgd_split_plan* plan) {
+  return plan && plan->threshold > 0 && plan->n_heavy > 0;
+}
+
+// Every check that does not depend on the element types, in the order that decides which message
+// a call with two faults gets: what a feature of the entry point needs, what every hop needs, and
+// what a row order excludes.
+inline hgd_status spmm_check_args(const SpmmRequest& r) {
+  const char* fn = r.fn;
+  const int32_t d = r.d;
+  const hgd_row_epilogue* ex = r.ex;
+  const bool empty = r.row_end == r.row_begin;
+  HGD_REQUIRE(!r.ordered || r.out_row || r.n_rows <= 0, "%s: null out_row", fn);
+  HGD_REQUIRE(!r.blocked || (r.n_blk >= 1 && r.n_blk <= 64), "%s: blocks must be 1..64", fn);
+  HGD_REQUIRE(!r.blocked || r.blk_start || r.row_end <= r.row_begin, "%s: null blk_start", fn);
+  HGD_REQUIRE(r.keep > 0.f, "%s: keep must be > 0 (got %g)", fn, (double)r.keep);  // (unmasked: 1)
+  HGD_REQUIRE(!r.masked || r.mask || empty, "%s: null mask", fn);
   HGD_REQUIRE(d > 0, "%s: d must be > 0 (got %d)", fn, d);
-  HGD_REQUIRE(n_rows >= 0 && n_src_rows >= 0, "%s: negative sizes", fn);
-  HGD_REQUIRE(row_begin >= 0 && row_begin <= row_end && row_end <= n_rows,
-              "%s: row range [%lld,%lld) outside [0,%lld)", fn, (long long)row_begin,
-              (long long)row_end, (long long)n_rows);
-  HGD_REQUIRE(ldx >= d && ldy >= d, "%s: ldx/ldy must be >= d", fn);
-  HGD_REQUIRE(epilogue >= HGD_EPI_NONE && epilogue <= HGD_EPI_RELU, "%s: bad epilogue %d", fn,
-              epilogue);
+  HGD_REQUIRE(r.n_rows >= 0 && r.n_src_rows >= 0, "%s: negative sizes", fn);
+  HGD_REQUIRE(r.row_begin >= 0 && r.row_begin <= r.row_end && r.row_end <= r.n_rows,
+              "%s: row range [%lld,%lld) outside [0,%lld)", fn, (long long)r.row_begin,
+              (long long)r.row_end, (long long)r.n_rows);
+  HGD_REQUIRE(r.ldx >= d && r.ldy >= d, "%s: ldx/ldy must be >= d", fn);
+  HGD_REQUIRE(r.epilogue >= HGD_EPI_NONE && r.epilogue <= HGD_EPI_RELU, "%s: bad epilogue %d", fn,
+              r.epilogue);
   if (ex) {
-    HGD_REQUIRE(epilogue == HGD_EPI_NONE || slope >= 0.f,
-                "%s: a fused activation needs slope >= 0 (got %g)", fn, (double)slope);
+    HGD_REQUIRE(r.epilogue == HGD_EPI_NONE || r.slope >= 0.f,
+                "%s: a fused activation needs slope >= 0 (got %g)", fn, (double)r.slope);
     HGD_REQUIRE(ex->layer_norm == 0 || ex->layer_norm == 1, "%s: layer_norm must be 0/1", fn);
     HGD_REQUIRE(!ex->res1 || ex->ld_res1 >= d, "%s: ld_res1 < d", fn);
     HGD_REQUIRE(!ex->res2 || ex->ld_res2 >= d, "%s: ld_res2 < d", fn);
@@ -179,49 +202,61 @@ inline hgd_status spmm_check_args(const char* fn, const void* rowptr, int64_t n_
     HGD_REQUIRE(!ex->sum_out || (ex->ld_sum_out >= d && ex->ld_sum_res >= d),
                 "%s: ld_sum_out / ld_sum_res < d", fn);
   }
-  if (row_end == row_begin) return HGD_OK;
-  // col / X may be NULL for a structure without nonzeros (never dereferenced then).
-  HGD_REQUIRE(rowptr && Y, "%s: null rowptr/Y", fn);
-  HGD_REQUIRE(X || n_src_rows == 0, "%s: null X", fn);
-  *run = true;
+  if (!empty) {
+    // col / X may be NULL for a structure without nonzeros (never dereferenced then); a blocked
+    // hop's row pointers are its blk_start, checked above
+    HGD_REQUIRE((r.rowptr || r.blocked) && r.Y, "%s: null rowptr/Y", fn);
+    HGD_REQUIRE(r.X || r.n_src_rows == 0, "%s: null X", fn);
+  }
+  if (r.out_row) {
+    // the ordered hop is the row kernel over every row: a split plan's chunks and fix-up and the
+    // segmented walk index Y by position, a row range is one of positions, and the fused
+    // epilogue's side tables and the blocked hop's passes are indexed by row
+    if (has_split_rows(r.plan) || (r.plan && (r.plan->flags & HGD_PLAN_SEGMENTED)))
+      return fail(HGD_ERR_UNSUPPORTED, "%s: no split rows or segmented walk with a row order", fn);
+    if (r.mask || ex || r.blocked)
+      return fail(HGD_ERR_UNSUPPORTED,
+                  "%s: no mask, fused row epilogue or source blocks with a row order", fn);
+    if (r.row_begin != 0 || r.row_end != r.n_rows)
+      return fail(HGD_ERR_UNSUPPORTED, "%s: a row order covers all rows, got [%lld,%lld) of %lld",
+                  fn, (long long)r.row_begin, (long long)r.row_end, (long long)r.n_rows);
+  }
   return HGD_OK;
 }
 
+// The kernels' argument block of a request (spmm_passes and launch_g set what changes from launch
+// to launch); the split plan is checked here, where its fields are read.
 template <class TX, class TY>
-hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const char* fn, const int64_t* rowptr,
-                          const int32_t* col, const float* val, const float* row_scale,
-                          int64_t row_begin, int64_t row_end, const TX* X, int64_t ldx, TY* Y,
-                          int64_t ldy, int32_t d, int32_t epilogue, float slope,
-                          const hgd_row_epilogue* ex, const uint8_t* mask, float keep,
-                          const hgd_split_plan* plan, void* workspace, size_t workspace_bytes) {
+hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const SpmmRequest& r) {
   const SpmmTuning& t = spmm_tuning();
-  a.rowptr = rowptr;
-  a.col = col;
-  a.val = val;
-  a.row_scale = row_scale;
-  a.row_begin = row_begin;
-  a.row_end = row_end;
-  a.X = X;
-  a.ldx = ldx;
-  a.Y = Y;
-  a.ldy = ldy;
-  a.d = d;
-  a.epi = epilogue;
-  a.slope = slope;
-  if (ex) a.ex = *ex;
-  a.mask = mask;
-  a.keep = keep;
-  {
-    int e2 = 0;
-    a.inv_keep = (!t.mask_div && keep > 0.f && std::frexp(keep, &e2) == 0.5f) ? 1.f / keep : 0.f;
-  }
+  a.rowptr = r.rowptr;
+  a.col = r.col;
+  a.val = r.val;
+  a.row_scale = r.row_scale;
+  a.row_begin = r.row_begin;
+  a.row_end = r.row_end;
+  a.X = static_cast<const TX*>(r.X);
+  a.ldx = r.ldx;
+  a.Y = static_cast<TY*>(r.Y);
+  a.ldy = r.ldy;
+  a.d = r.d;
+  a.epi = r.epilogue;
+  a.slope = r.slope;
+  if (r.ex) a.ex = *r.ex;
+  a.mask = r.mask;
+  a.keep = r.keep;
+  int e2 = 0;  // a power of two: the kept weights are multiplied by its exact inverse
+  const bool pow2 = !t.mask_div && r.keep > 0.f && std::frexp(r.keep, &e2) == 0.5f;
+  a.inv_keep = pow2 ? 1.f / r.keep : 0.f;
   a.mask_pair = t.mask_pair;
-  if (plan && plan->threshold > 0 && plan->n_heavy > 0) {
+  a.out_row = r.out_row;
+  const hgd_split_plan* plan = r.plan;
+  if (has_split_rows(plan)) {
     HGD_REQUIRE(plan->chunk > 0 && plan->heavy_rows && plan->heavy_cptr && plan->chunk_heavy,
-                "%s: incomplete split plan", fn);
-    const size_t need = hgd_spmm_workspace_size(plan, d);  // fp32 partials whatever TX / TY
-    if (workspace_bytes < need || (need && !workspace))
-      return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes,
+                "%s: incomplete split plan", r.fn);
+    const size_t need = hgd_spmm_workspace_size(plan, r.d);  // fp32 partials whatever TX / TY
+    if (r.workspace_bytes < need || (need && !r.workspace))
+      return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", r.fn, r.workspace_bytes,
                   need);
     a.heavy_threshold = plan->threshold;
     a.chunk = plan->chunk;
@@ -230,8 +265,8 @@ hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const char* fn, const int64_t* r
     a.chunk_heavy = plan->chunk_heavy;
     a.heavy_rows = plan->heavy_rows;
     a.heavy_cptr = plan->heavy_cptr;
-    a.partial = static_cast<float*>(workspace);
-  } else if (plan && (plan->flags & HGD_PLAN_SEGMENTED) && !mask) {
+    a.partial = static_cast<float*>(r.workspace);
+  } else if (plan && (plan->flags & HGD_PLAN_SEGMENTED) && !r.mask) {
     a.seg = 1;  // only without split rows: the segmented walk covers every nonzero of its rows
   }
   return HGD_OK;
@@ -241,13 +276,13 @@ hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const char* fn, const int64_t* r
 // row, and a pass (a launch, or one of an interleaved launch's) step = vec·G columns.
 struct SpmmPassPlan {
   bool aligned;  // 16-byte rows: the vector path
-  int vec, G, step;
+  int G, step;
 };
 
-// sx / sy: element sizes of X and Y; blocked: the source-blocked hop (hgd_spmm_blocked).
-inline hgd_status spmm_pass_plan(const char* fn, const void* X, int64_t ldx, size_t sx,
-                                 const void* Y, int64_t ldy, size_t sy, int32_t d,
-                                 const hgd_row_epilogue* ex, bool blocked, SpmmPassPlan* p) {
+// sx / sy: element sizes of X and Y.
+inline hgd_status spmm_pass_plan(const SpmmRequest& r, size_t sx, size_t sy, SpmmPassPlan* p) {
+  const int32_t d = r.d;
+  const hgd_row_epilogue* ex = r.ex;
   auto al16 = [](const void* ptr, int64_t ld, size_t size) {
     return ptr == nullptr || (reinterpret_cast<uintptr_t>(ptr) % 16 == 0 &&
                               ld % static_cast<int64_t>(16 / size) == 0);
@@ -256,7 +291,7 @@ inline hgd_status spmm_pass_plan(const char* fn, const void* X, int64_t ldx, siz
   // one access of a bf16 row, two of an fp32 row
   const bool f32 = sx == 4 && sy == 4;
   const int vec = f32 ? 4 : 8;
-  bool aligned = al16(X, ldx, sx) && al16(Y, ldy, sy) && d % vec == 0;
+  bool aligned = al16(r.X, r.ldx, sx) && al16(r.Y, r.ldy, sy) && d % vec == 0;
   if (ex)
     aligned = aligned && al16(ex->res1, ex->ld_res1, 4) && al16(ex->res2, ex->ld_res2, 4) &&
               al16(ex->act_out, ex->ld_act, 4) && al16(ex->sum_out, ex->ld_sum_out, 4) &&
@@ -264,10 +299,9 @@ inline hgd_status spmm_pass_plan(const char* fn, const void* X, int64_t ldx, siz
   if (ex && ex->layer_norm && (aligned ? d > 256 : d > 64))
     return fail(HGD_ERR_UNSUPPORTED,
                 "%s: layer_norm needs d <= 256 (16-byte aligned rows) or d <= 64 (got d=%d%s)",
-                fn, d, aligned ? "" : ", unaligned");
+                r.fn, d, aligned ? "" : ", unaligned");
   p->aligned = aligned;
   if (!aligned) {  // a column per lane
-    p->vec = 1;
     p->G = d >= 64 ? 64 : next_pow2(d);
     p->step = p->G;
     return HGD_OK;
@@ -278,7 +312,7 @@ inline hgd_status spmm_pass_plan(const char* fn, const void* X, int64_t ldx, siz
   int G = lanes >= 64 ? 64 : next_pow2(lanes);
   int pass_cols = spmm_tuning().pass_cols;  // HGD_TUNE_SPMM_PASS_COLS overrides every default
   if (pass_cols == 0) {
-    if (blocked) {
+    if (r.blocked) {
       // source-blocked: every pass runs the blocks in order, the later ones adding;
       // passes of up to 128 columns: at d = 256 the blocked hop into items takes
       // 16.99 ms in 128-column passes, 18.04 in 64-column ones and 19.54 in one 256-wide pass
@@ -296,44 +330,42 @@ inline hgd_status spmm_pass_plan(const char* fn, const void* X, int64_t ldx, siz
     }
   }
   if (!ex && vec * G > pass_cols) G = pass_cols / vec;
-  p->vec = vec;
   p->G = G;
   p->step = vec * G;
   return HGD_OK;
 }
 
-// The column passes of one hop over VEC-column lanes. The fused epilogue (fused), the source
-// blocks (blk_seg: the block-major blk_start, n_blk of them over n_rows rows each) and the
-// interleaved single launch are fp32-only: HGD_TUNE_SPMM_PASS_INTERLEAVE and
+// The column passes of one hop over VEC-column lanes. The fused epilogue, the source blocks and
+// the interleaved single launch are fp32-only: HGD_TUNE_SPMM_PASS_INTERLEAVE and
 // HGD_TUNE_SPMM_BLOCKED_SEG have no effect on a 16-bit hop.
 template <int VEC, class TX, class TY>
-hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmLaunch& L, const SpmmPassPlan& p,
-                       bool fused, const int64_t* blk_seg, int32_t n_blk, int64_t n_rows) {
-  const int32_t d = a.d, epilogue = a.epi;
+hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmRequest& r, const SpmmPassPlan& p) {
+  const int32_t d = a.d;
+  const bool fused = r.ex != nullptr;
   if constexpr (kF32<TX, TY> && VEC == 4) {
     const int n_pass = (d + p.step - 1) / p.step;
-    if (spmm_tuning().pass_interleave && n_pass > 1 && !fused && !blk_seg && !a.mask &&
+    if (spmm_tuning().pass_interleave && n_pass > 1 && !fused && !r.blocked && !a.mask &&
         a.n_chunks == 0 && !a.seg) {
       a.col0 = 0;
       a.n_pass = n_pass;
       a.pass_cols = p.step;
-      return launch_vec<VEC, false>(p.G, a, L);
+      return launch_vec<VEC, false>(p.G, a, r);
     }
   }
   for (int c0 = 0; c0 < d; c0 += p.step) {
     a.col0 = c0;
-    for (int k = 0; k < (blk_seg ? n_blk : 1); ++k) {
+    for (int k = 0; k < (r.blocked ? r.n_blk : 1); ++k) {
       hgd_status s;
       if constexpr (kF32<TX, TY>) {
-        if (blk_seg) {
-          a.rowptr = blk_seg + static_cast<int64_t>(k) * n_rows;  // block k's own CSR
+        if (r.blocked) {
+          a.rowptr = r.blk_start + static_cast<int64_t>(k) * r.n_rows;  // block k's own CSR
           if (VEC == 4) a.seg = spmm_tuning().blocked_seg;  // (the vector path's only)
           a.blk_accum = k > 0;
-          a.epi = k + 1 == n_blk ? epilogue : HGD_EPI_NONE;  // the activation after the last
+          a.epi = k + 1 == r.n_blk ? r.epilogue : HGD_EPI_NONE;  // the activation after the last
         }
-        s = fused ? launch_vec<VEC, true>(p.G, a, L) : launch_vec<VEC, false>(p.G, a, L);
+        s = fused ? launch_vec<VEC, true>(p.G, a, r) : launch_vec<VEC, false>(p.G, a, r);
       } else {
-        s = launch_vec<VEC, false>(p.G, a, L);
+        s = launch_vec<VEC, false>(p.G, a, r);
       }
       if (s != HGD_OK) return s;
     }
@@ -341,48 +373,19 @@ hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmLaunch& L, const SpmmPassP
   return HGD_OK;
 }
 
-// The hop behind every entry point: fn is the entry point's name, ex the fused row epilogue or
-// NULL, mask / keep the edge-dropped view or NULL / 1, and blk_seg (hgd_spmm_blocked) the
-// block-major blk_start (rowptr is the same pointer) with col / val the block-major arrays.
+// The hop behind every entry point, over a table of TX and an output of TY.
 template <class TX, class TY>
-hgd_status spmm_launch(const int64_t* rowptr, const int32_t* col, const float* val,
-                       const float* row_scale, int64_t n_rows, int64_t n_src_rows,
-                       int64_t row_begin, int64_t row_end, const TX* X, int64_t ldx, TY* Y,
-                       int64_t ldy, int32_t d, int32_t epilogue, float slope,
-                       const hgd_row_epilogue* ex, const uint8_t* mask, float keep,
-                       const hgd_split_plan* plan, void* workspace, size_t workspace_bytes,
-                       void* stream, const char* fn, const int64_t* blk_seg = nullptr,
-                       int32_t n_blk = 0, const int32_t* out_row = nullptr) {
-  bool run = false;
-  hgd_status s = spmm_check_args(fn, rowptr, n_rows, n_src_rows, row_begin, row_end, X, ldx, Y,
-                                 ldy, d, epilogue, slope, ex, &run);
-  if (s != HGD_OK) return s;
-  if (out_row) {
-    // the ordered hop (hgd_spmm_ordered) is the row kernel over every row: a split plan's chunks
-    // and fix-up and the segmented walk index Y by position, a row range is one of positions, and
-    // the fused epilogue's side tables and the blocked hop's passes are indexed by row
-    if ((plan && plan->threshold > 0 && plan->n_heavy > 0) ||
-        (plan && (plan->flags & HGD_PLAN_SEGMENTED)))
-      return fail(HGD_ERR_UNSUPPORTED, "%s: no split rows or segmented walk with a row order", fn);
-    if (mask || ex || blk_seg)
-      return fail(HGD_ERR_UNSUPPORTED,
-                  "%s: no mask, fused row epilogue or source blocks with a row order", fn);
-    if (row_begin != 0 || row_end != n_rows)
-      return fail(HGD_ERR_UNSUPPORTED, "%s: a row order covers all rows, got [%lld,%lld) of %lld",
-                  fn, (long long)row_begin, (long long)row_end, (long long)n_rows);
-  }
-  if (!run) return s;
+hgd_status spmm_launch(const SpmmRequest& r) {
+  hgd_status s = spmm_check_args(r);
+  if (s != HGD_OK || r.row_end == r.row_begin) return s;  // (an empty range: nothing to launch)
   SpmmArgsT<TX, TY> a{};
-  s = spmm_fill_args(a, fn, rowptr, col, val, row_scale, row_begin, row_end, X, ldx, Y, ldy, d,
-                     epilogue, slope, ex, mask, keep, plan, workspace, workspace_bytes);
+  s = spmm_fill_args(a, r);
   if (s != HGD_OK) return s;
-  a.out_row = out_row;
   SpmmPassPlan p;
-  s = spmm_pass_plan(fn, X, ldx, sizeof(TX), Y, ldy, sizeof(TY), d, ex, blk_seg != nullptr, &p);
+  s = spmm_pass_plan(r, sizeof(TX), sizeof(TY), &p);
   if (s != HGD_OK) return s;
-  const SpmmLaunch L{fn, val != nullptr, as_stream(stream)};
-  if (!p.aligned) return spmm_passes<1>(a, L, p, ex != nullptr, blk_seg, n_blk, n_rows);
-  return spmm_passes<kF32<TX, TY> ? 4 : 8>(a, L, p, ex != nullptr, blk_seg, n_blk, n_rows);
+  if (!p.aligned) return spmm_passes<1>(a, r, p);
+  return spmm_passes<kF32<TX, TY> ? 4 : 8>(a, r, p);
 }
 
 }  // namespace hgd
