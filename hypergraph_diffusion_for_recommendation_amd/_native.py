@@ -244,6 +244,11 @@ _SIGNATURES = {
     "hgd_spmm_blocked": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64,
                                  c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32, c_f32,
                                  c_i32, c_void_p]),
+    "hgd_spmm_blocked_dt_workspace_size": (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    "hgd_spmm_blocked_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64,
+                                    c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i32, c_i64, c_i32,
+                                    c_i32, c_f32, c_i32, c_void_p, c_size, c_void_p]),
+    "hgd_spmm_blocks_for_dt": (c_i32, [c_i64, c_i32, c_i32]),
     "hgd_spmm_row_order_for": (c_i32, [c_i64, c_i64, c_i64, c_i32]),
     "hgd_spmm_row_order_workspace_size": (c_size, [c_i64]),
     "hgd_spmm_row_order": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p,

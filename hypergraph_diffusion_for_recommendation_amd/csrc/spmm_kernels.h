@@ -59,6 +59,13 @@ struct SpmmArgsT {
   // position r indexes rowptr / row_scale (the ordered copies) and the row is written to Y row
   // out_row[r]; NULL: Y row r
   const int32_t* out_row;
+  // source-blocked hop into a 16-bit Y (hgd_spmm_blocked_dt; read by the 16-bit-TY instantiations
+  // only): the running partial of a row lives in fp32 at blk_part + row·ld_part, not in Y — block
+  // 0 writes it, the blocks between add to it, and the last block (blk_last) adds it, applies the
+  // activation and stores Y once, so Y is rounded once. NULL: Y is written directly
+  float* blk_part;
+  int64_t ld_part;
+  int32_t blk_last;
 };
 using SpmmArgs = SpmmArgsT<>;
 
@@ -84,27 +91,47 @@ constexpr int kPolPrefetch = 8;  // software-pipelined index batches (see gather
 // yr is its row of Y (r, or the ordered hop's out_row[r]).
 // With EX the hgd_row_epilogue runs in registers: the group holds the whole row (single column
 // pass, checked on the host), so the LayerNorm statistics are two group_sum butterflies.
-template <int G, int VEC, bool EX, bool NT_STORE, class TX = float, class TY = float>
+// BLK_PART: the caller can be a launch of a source-blocked hop into a 16-bit Y (the row kernel
+// without a mask only: the others are the code they were).
+template <int G, int VEC, bool EX, bool NT_STORE, class TX = float, class TY = float,
+          bool BLK_PART = false>
 __device__ __forceinline__ void finish_row(const SpmmArgsT<TX, TY>& a, int64_t r, int64_t yr,
                                            float s, int l, int64_t coff, bool col_ok,
                                            float (&acc)[VEC]) {
+  // a 16-bit Y of a source-blocked hop keeps its running partial in the fp32 scratch (blk_part)
+  constexpr bool PART = BLK_PART && !EX && sizeof(TY) == 2;
   if constexpr (!EX) {
     if (a.blk_accum) {  // a later block of a column-blocked hop: Y = epi(s·Σ_block + Y)
       float prev[VEC];
       if (col_ok) {
-        load_vec<VEC>(a.Y + yr * a.ldy + coff, prev);
+        if constexpr (PART)
+          load_vec<VEC>(a.blk_part + yr * a.ld_part + coff, prev);
+        else
+          load_vec<VEC>(a.Y + yr * a.ldy + coff, prev);
       } else {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) prev[i] = 0.f;
       }
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = epilogue(acc[i] * s + prev[i], a.epi, a.slope);
+      if constexpr (PART) {
+        if (!a.blk_last) {  // (the activation is HGD_EPI_NONE before the last block)
+          if (col_ok) store_vec<VEC>(a.blk_part + yr * a.ld_part + coff, acc);
+          return;
+        }
+      }
       if (col_ok) store_vec<VEC, NT_STORE>(a.Y + yr * a.ldy + coff, acc);
       return;
     }
   }
 #pragma unroll
   for (int i = 0; i < VEC; ++i) acc[i] = epilogue(acc[i] * s, a.epi, a.slope);
+  if constexpr (PART) {
+    if (a.blk_part && !a.blk_last) {  // block 0 of several: the partial starts in the scratch
+      if (col_ok) store_vec<VEC>(a.blk_part + yr * a.ld_part + coff, acc);
+      return;
+    }
+  }
   if constexpr (EX) {
     const hgd_row_epilogue& e = a.ex;
     if (e.act_out && col_ok) store_vec<VEC>(e.act_out + r * e.ld_act + coff, acc);
@@ -466,7 +493,8 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgsT<TX, TY> a) {
   masked_or_plain_sum<G, VEC, U, HAS_VAL, POL, MASK>(a, e0, e1, l, col_ok, acc, col0);
   const int64_t yr = ORD ? static_cast<int64_t>(orow) : r;
   const float s = a.row_scale ? a.row_scale[r] : 1.f;
-  finish_row<G, VEC, EX, (POL & kPolNtStore) != 0>(a, r, yr, s, l, coff, col_ok, acc);
+  finish_row<G, VEC, EX, (POL & kPolNtStore) != 0, TX, TY, !MASK>(a, r, yr, s, l, coff, col_ok,
+                                                                   acc);
 }
 
 // Segmented variant for short rows (hgd_split_plan.flags & HGD_PLAN_SEGMENTED): a group owns

@@ -40,7 +40,8 @@ struct SpmmRequest {
   int32_t epilogue;  // HGD_EPI_*
   float slope;
   const hgd_split_plan* plan = nullptr;
-  void* workspace = nullptr;  // of the plan's split rows
+  // of the plan's split rows; of a blocked hop into a 16-bit Y, its fp32 partials (blocked_part)
+  void* workspace = nullptr;
   size_t workspace_bytes = 0;
   void* stream = nullptr;
   const hgd_row_epilogue* ex = nullptr;  // the fused row epilogue
@@ -165,6 +166,14 @@ hgd_status launch_vec(int G, const SpmmArgsT<TX, TY>& a, const SpmmRequest& r) {
   }
 }
 
+// The fp32 scratch a source-blocked hop into a 16-bit Y keeps its running partials in (sy: the
+// element size of Y): every row of Y at full width, indexed as Y is, so a row range touches only
+// its own rows. 0 for an fp32 Y (it holds its own partial) and for one block.
+inline size_t blocked_part_bytes(int64_t n_rows, int32_t d, size_t sy, int32_t n_blk) {
+  if (sy != 2 || n_blk <= 1 || n_rows <= 0 || d <= 0) return 0;
+  return align_up(static_cast<size_t>(n_rows) * static_cast<size_t>(d) * 4);
+}
+
 inline bool has_split_rows(const hgd_split_plan* plan) {
   return plan && plan->threshold > 0 && plan->n_heavy > 0;
 }
@@ -269,6 +278,16 @@ hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const SpmmRequest& r) {
   } else if (plan && (plan->flags & HGD_PLAN_SEGMENTED) && !r.mask) {
     a.seg = 1;  // only without split rows: the segmented walk covers every nonzero of its rows
   }
+  if constexpr (sizeof(TY) == 2) {
+    if (r.blocked) {  // (a blocked hop has no plan: the workspace is its partials')
+      const size_t need = blocked_part_bytes(r.n_rows, r.d, sizeof(TY), r.n_blk);
+      if (r.workspace_bytes < need || (need && !r.workspace))
+        return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", r.fn, r.workspace_bytes,
+                    need);
+      a.blk_part = need ? static_cast<float*>(r.workspace) : nullptr;
+      a.ld_part = r.d;
+    }
+  }
   return HGD_OK;
 }
 
@@ -292,6 +311,8 @@ inline hgd_status spmm_pass_plan(const SpmmRequest& r, size_t sx, size_t sy, Spm
   const bool f32 = sx == 4 && sy == 4;
   const int vec = f32 ? 4 : 8;
   bool aligned = al16(r.X, r.ldx, sx) && al16(r.Y, r.ldy, sy) && d % vec == 0;
+  // (the partials of a blocked hop into a 16-bit Y: fp32 rows of d)
+  if (r.blocked && sy == 2 && r.n_blk > 1) aligned = aligned && al16(r.workspace, d, 4);
   if (ex)
     aligned = aligned && al16(ex->res1, ex->ld_res1, 4) && al16(ex->res2, ex->ld_res2, 4) &&
               al16(ex->act_out, ex->ld_act, 4) && al16(ex->sum_out, ex->ld_sum_out, 4) &&
@@ -335,9 +356,9 @@ inline hgd_status spmm_pass_plan(const SpmmRequest& r, size_t sx, size_t sy, Spm
   return HGD_OK;
 }
 
-// The column passes of one hop over VEC-column lanes. The fused epilogue, the source blocks and
-// the interleaved single launch are fp32-only: HGD_TUNE_SPMM_PASS_INTERLEAVE and
-// HGD_TUNE_SPMM_BLOCKED_SEG have no effect on a 16-bit hop.
+// The column passes of one hop over VEC-column lanes. The fused epilogue and the interleaved single
+// launch are fp32-only, as is the segmented walk of a source block's rows:
+// HGD_TUNE_SPMM_PASS_INTERLEAVE and HGD_TUNE_SPMM_BLOCKED_SEG have no effect on a 16-bit hop.
 template <int VEC, class TX, class TY>
 hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmRequest& r, const SpmmPassPlan& p) {
   const int32_t d = a.d;
@@ -356,13 +377,16 @@ hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmRequest& r, const SpmmPass
     a.col0 = c0;
     for (int k = 0; k < (r.blocked ? r.n_blk : 1); ++k) {
       hgd_status s;
-      if constexpr (kF32<TX, TY>) {
-        if (r.blocked) {
-          a.rowptr = r.blk_start + static_cast<int64_t>(k) * r.n_rows;  // block k's own CSR
+      if (r.blocked) {
+        a.rowptr = r.blk_start + static_cast<int64_t>(k) * r.n_rows;  // block k's own CSR
+        if constexpr (kF32<TX, TY>) {
           if (VEC == 4) a.seg = spmm_tuning().blocked_seg;  // (the vector path's only)
-          a.blk_accum = k > 0;
-          a.epi = k + 1 == r.n_blk ? r.epilogue : HGD_EPI_NONE;  // the activation after the last
         }
+        a.blk_accum = k > 0;
+        a.epi = k + 1 == r.n_blk ? r.epilogue : HGD_EPI_NONE;  // the activation after the last
+        a.blk_last = k + 1 == r.n_blk;  // (read for a 16-bit Y only: it then leaves the scratch)
+      }
+      if constexpr (kF32<TX, TY>) {
         s = fused ? launch_vec<VEC, true>(p.G, a, r) : launch_vec<VEC, false>(p.G, a, r);
       } else {
         s = launch_vec<VEC, false>(p.G, a, r);

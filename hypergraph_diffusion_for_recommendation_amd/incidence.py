@@ -239,8 +239,9 @@ class CSR:
         return self.rowptr[1:] - self.rowptr[:-1]
 
 
-def spmm_blocks(csr: CSR, d: int) -> int:
-    """How many source blocks the hop over ``csr`` at width ``d`` runs in (0 = one pass).
+def spmm_blocks(csr: CSR, d: int, x_dtype: torch.dtype = torch.float32) -> int:
+    """How many source blocks the hop over ``csr`` at width ``d`` gathering a table of
+    ``x_dtype`` runs in (0 = one pass).
 
     The hop gathers one d-wide row of X per nonzero at random. When X is small enough for the
     256 MB Infinity Cache (the item table a hop into users reads: 256 MB at d = 64) the gathers
@@ -258,17 +259,26 @@ def spmm_blocks(csr: CSR, d: int) -> int:
 
     Only for a structure whose rows' columns ascend (the CSC of an Incidence), without split
     rows or the segmented walk. ``HGD_SPMM_BLOCKS``: ``0`` turns it off, an integer P forces P
-    blocks (1 = off) wherever it applies, unset = the size rule."""
+    blocks (1 = off) wherever it applies, a 16-bit hop (hgd_spmm_blocked_dt) included, unset =
+    the size rule. The rule is by the table's element type (hgd_spmm_blocks_for_dt): the
+    constants above were measured over 4-byte rows; over a bfloat16 table no block count beat
+    the plain hop at the same shapes (d = 64: 2.83 ms plain, 2.88 at P = 2, 3.05 at P = 4;
+    DESIGN.md §4.1), so the rule never blocks one."""
+    if x_dtype not in _HOP_DTYPES:
+        raise TypeError(f"spmm_blocks: x_dtype must be float32 or bfloat16, got {x_dtype}")
     if not csr.cols_ascending or csr.n_heavy or csr.segmented or csr.nnz == 0:
         return 0
+    if getattr(csr, "mask", None) is not None:
+        return 0  # an edge-dropped view's hop is the masked kernel: spmm_csr never blocks it
     env = os.environ.get("HGD_SPMM_BLOCKS", "")
     if env not in ("", "auto"):
         p = int(env)
         if p < 0 or p > 64:
             raise ValueError(f"HGD_SPMM_BLOCKS must be 0..64, got {env!r}")
         return p if p > 1 else 0
-    # the library's size rule (hgd_spmm_blocks_for), shared with the native incidence objects
-    return int(nat.load().hgd_spmm_blocks_for(csr.n_cols, int(d)))
+    # the library's size rule (hgd_spmm_blocks_for_dt; for a float32 table hgd_spmm_blocks_for's,
+    # which the native incidence objects share)
+    return int(nat.load().hgd_spmm_blocks_for_dt(csr.n_cols, int(d), _HOP_DTYPES[x_dtype]))
 
 
 def spmm_row_order(csr: CSR, d: int) -> bool:
@@ -309,7 +319,8 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     ``out_dtype``, else ``X.dtype``. Float32 in and out is hgd_spmm (and its masked / blocked /
     fused forms); a bfloat16 side is hgd_spmm_dt / hgd_spmm_masked_dt: the same fp32 sums over
     exactly widened elements, a bf16 result rounded to nearest even on the store. A bf16 hop has
-    no fused row epilogue (``ex``) and never runs source-blocked.
+    no fused row epilogue (``ex``); source-blocked it is hgd_spmm_blocked_dt, whose bf16 result is
+    still the fp32 result rounded once (the blocks' partials stay fp32, in a scratch).
 
     With ``ex`` (an ``hgd_row_epilogue``) the call is ``hgd_spmm_fused``: ``ex.act``/``ex.slope``
     replace ``epilogue``/``slope`` and the LayerNorm / residual epilogue runs in the store.
@@ -355,10 +366,10 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     if timer is not None:
         t0 = timer.begin()
     mask = getattr(csr, "mask", None)
-    if mask is not None or ex is not None or blocks == 0 or dt:
-        blocks = 0  # (the size rule was measured for fp32 tables: a 16-bit hop is never blocked)
+    if mask is not None or ex is not None or blocks == 0:
+        blocks = 0
     else:
-        blocks = spmm_blocks(csr, d)
+        blocks = spmm_blocks(csr, d, X.dtype)
     # the arguments the entry points share, evaluated once: the structure (a masked one adds its
     # mask and keep rate), row scale and row range, the table and the output, workspace and stream.
     # (Plain locals passed positionally: packing them into tuples and unpacking those into the
@@ -384,6 +395,16 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
             rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, _HOP_DTYPES[X.dtype], ldx, yp,
             _HOP_DTYPES[y_dtype], ldy, d, int(epilogue), float(slope), plan_ptr, wp, wsb, st),
             "hgd_spmm_masked_dt")
+    elif dt and blocks:
+        start, bcol, _ = csr.col_blocks(blocks)
+        bval = csr.blocked_values(blocks, val)
+        # a bf16 output keeps its fp32 running partials in a scratch (an fp32 one in itself)
+        pb = lib.hgd_spmm_blocked_dt_workspace_size(n, d, _HOP_DTYPES[y_dtype], blocks)
+        part = _ws(pb, X.device) if pb else None
+        nat.check(lib.hgd_spmm_blocked_dt(
+            start.data_ptr(), bcol.data_ptr(), nat.ptr(bval), sp, n, m, rb, re_, xp,
+            _HOP_DTYPES[X.dtype], ldx, yp, _HOP_DTYPES[y_dtype], ldy, d, int(epilogue),
+            float(slope), blocks, nat.ptr(part), pb, st), "hgd_spmm_blocked_dt")
     elif dt:
         nat.check(lib.hgd_spmm_dt(
             rp, cp, vp, sp, n, m, rb, re_, xp, _HOP_DTYPES[X.dtype], ldx, yp,

@@ -40,13 +40,19 @@ def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
     """Bytes the hgd_spmm launch streams at minimum as implemented (int64 rowptr, weights).
     A source-blocked hop (hgd_spmm_blocked, ``blocks`` = P > 1) reads the [R × (P+1)] int64
     block starts instead of the rowptr, writes every Y row P times, reads it back P−1 times and
-    applies the row scale in every pass. An ordered hop (hgd_spmm_ordered) also reads the int32
-    output row of every row."""
+    applies the row scale in every pass. A blocked hop into a 16-bit Y (hgd_spmm_blocked_dt)
+    keeps the running partial in an fp32 scratch instead: P−1 writes and P−1 reads of 4-byte
+    rows, then one store of the 2-byte Y row. An ordered hop (hgd_spmm_ordered) also reads the
+    int32 output row of every row."""
     if ordered:
         return impl_bytes(nnz, rows, d, has_val, has_scale, 0, x_bytes, y_bytes) + rows * 4
     if blocks > 1:
+        if y_bytes == 4:
+            y_traffic = 4 * d * (2 * blocks - 1)
+        else:
+            y_traffic = 4 * d * (2 * blocks - 2) + y_bytes * d
         return (nnz * (4 + (4 if has_val else 0) + x_bytes * d)
-                + rows * (y_bytes * d * (2 * blocks - 1) + (4 * blocks if has_scale else 0))
+                + rows * (y_traffic + (4 * blocks if has_scale else 0))
                 + rows * (blocks + 1) * 8)
     return (nnz * (4 + (4 if has_val else 0) + x_bytes * d)
             + rows * (y_bytes * d + (4 if has_scale else 0)) + (rows + 1) * 8)

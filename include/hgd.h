@@ -16,6 +16,7 @@
  *   hgd_spmm_blocked         the same torch.sparse.mm(adj.t(), X) hop for a gathered table larger
  *                            than the Infinity Cache (source-blocked; hgd_spmm_col_blocks builds
  *                            its block-major copy of the CSC)
+ *   hgd_spmm_blocked_dt      the source-blocked hop over bfloat16 tables
  *   hgd_sort_perm            COO→CSR / CSR→CSC ordering that cuSPARSE re-derives per call
  *                            (`adj.t()` in HGCNConv.forward, HGNN_HD4.py:459; coalesce in torch.sparse.mm)
  *   hgd_rowptr_from_sorted   row pointer of a row-sorted COO  base/torch_interface.py:8-12
@@ -34,8 +35,8 @@
  *   - Errors come back as hgd_status; hgd_get_last_error_string() describes the last failure
  *     on the calling thread. No C++ exception crosses the ABI.
  *   - Indices: row pointers are int64, column/row indices are int32 (rows, cols < 2^31).
- *   - Floating point is fp32 in and out (hgd_spmm_dt / hgd_spmm_masked_dt also take bfloat16
- *     tables); sums run in fp32 in edge order (deterministic).
+ *   - Floating point is fp32 in and out (hgd_spmm_dt / hgd_spmm_masked_dt / hgd_spmm_blocked_dt also
+ *     take bfloat16 tables); sums run in fp32 in edge order (deterministic).
  */
 #ifndef HGD_H
 #define HGD_H
@@ -260,6 +261,42 @@ hgd_status hgd_spmm_blocked(const int64_t* blk_start, const int32_t* blk_col,
                             int64_t n_src_rows, int64_t row_begin, int64_t row_end,
                             const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d,
                             int32_t epilogue, float slope, int32_t n_blocks, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * hgd_spmm_blocked over tables stored in bfloat16 (x_dtype / y_dtype as hgd_spmm_dt, over the same
+ * block-major copy of hgd_spmm_col_blocks). Replaces the same call sites as hgd_spmm
+ * (torch.sparse.mm(adj, X), model/graph/HCCF.py:199; torch.sparse.mm(adj.t(), X),
+ * model/graph/HGNN_HD4.py:459-462, model/graph/HGCN.py:173-175) when the embedding table is kept
+ * or staged in 16 bits AND is too large for the Infinity Cache (a 10 M × 64 bf16 table: 1.28 GB).
+ * f32 / f32 codes forward to hgd_spmm_blocked (bitwise its output); n_blocks = 1 is bitwise
+ * hgd_spmm_dt without a plan.
+ *   fp32 Y: the running partial of a row lives in Y, as in hgd_spmm_blocked; no workspace.
+ *   bf16 Y: the partial must not be rounded per block, so it lives in an fp32 scratch in
+ *     `workspace`: block 0 writes it, the blocks between add to it, the last block adds it, applies
+ *     the activation and stores Y once. A bf16 Y is therefore the fp32 Y of the same call rounded
+ *     to nearest even, bit for bit. The scratch is indexed by row as Y is (a row range touches
+ *     only its own rows) at the hop's full width: hgd_spmm_blocked_dt_workspace_size is
+ *     n_rows·d·4 bytes rounded up to 256 (0 for an fp32 Y and for n_blocks <= 1). The full width,
+ *     not one column pass's: the pass width follows the alignment of the call's pointers and the
+ *     tuning, which a size query does not see. The 16-byte path also needs the workspace 16-byte
+ *     aligned. Too small a workspace: HGD_ERR_WORKSPACE.
+ * The call allocates nothing and does not synchronise (graph-capturable). HGD_TUNE_SPMM_BLOCKED_SEG
+ * has no effect on a 16-bit hop.
+ *
+ * hgd_spmm_blocks_for_dt: the size rule by the table's element type. HGD_DT_F32 answers as
+ * hgd_spmm_blocks_for; a 16-bit table answers 0: measured on MI355X, no block
+ * count from 2 to 8 beat the plain bf16 hop over a 1.28, 2.56 or 5.12 GB table.
+ * ---------------------------------------------------------------------------------------- */
+size_t hgd_spmm_blocked_dt_workspace_size(int64_t n_rows, int32_t d, int32_t y_dtype,
+                                          int32_t n_blocks);
+hgd_status hgd_spmm_blocked_dt(const int64_t* blk_start, const int32_t* blk_col,
+                               const float* blk_val, const float* row_scale, int64_t n_rows,
+                               int64_t n_src_rows, int64_t row_begin, int64_t row_end,
+                               const void* X, int32_t x_dtype, int64_t ldx, void* Y,
+                               int32_t y_dtype, int64_t ldy, int32_t d, int32_t epilogue,
+                               float slope, int32_t n_blocks, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int32_t hgd_spmm_blocks_for_dt(int64_t n_src_rows, int32_t d, int32_t x_dtype);
 
 /* ------------------------------------------------------------------------------------------
  * The same hop (hgd_spmm, every row, fp32) with the rows WALKED in ascending order of their

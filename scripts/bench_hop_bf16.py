@@ -3,7 +3,9 @@
 Hᵀ·X over the CSC, gathering the user table; into users: H·M over the CSR, gathering the item
 table) this times the fp32 hop as the library runs it (source-blocked into items under the size
 rule; HGD_SPMM_BLOCKS=0 in the environment makes it the plain hgd_spmm), the plain fp32 hop where
-that differs, and the bf16→bf16 hop (hgd_spmm_dt), on the same structure, weights and row scales.
+that differs, the bf16→bf16 hop (hgd_spmm_dt) and, where the structure allows blocking, the same
+hop in --bf16-blocks source blocks (hgd_spmm_blocked_dt), on the same structure, weights and row
+scales.
 
 The variants alternate inside every round of one process (after untimed warm-up rounds); a
 sample is --reps back-to-back launches between two device events. Reported per variant: median,
@@ -36,6 +38,9 @@ def main():
                     help="item popularity exponent of bench.py's generator (default: uniform)")
     ap.add_argument("--pass-cols", type=int, default=0,
                     help="HGD_TUNE_SPMM_PASS_COLS for every variant (0 = the default passes)")
+    ap.add_argument("--bf16-blocks", type=int, default=4,
+                    help="source blocks of the blocked bf16 column (hgd_spmm_blocked_dt, timed "
+                         "wherever the structure allows blocking; 0 = no such column)")
     args = ap.parse_args()
 
     import torch
@@ -46,6 +51,7 @@ def main():
     from hypergraph_diffusion_for_recommendation_amd.incidence import spmm_blocks, spmm_csr
 
     nat.check(nat.load().hgd_set_tuning(3, args.pass_cols), "pass cols")
+    env_blocks = os.environ.get("HGD_SPMM_BLOCKS", "")  # ("" reads as unset: the size rule)
     dev = torch.device("cuda:0")
     U, I, d = args.users, args.items, args.dim
     idx = bench.make_graph(U, I, args.edges, 0, args.zipf, dev)
@@ -70,11 +76,22 @@ def main():
         variants = {"fp32": (X32r, None, 4)}
         if P:  # the library blocks this hop: also time the plain one
             variants["fp32_plain"] = (X32r, 0, 4)
-        variants["bf16"] = (X16, None, 2)
+        variants["bf16"] = (X16, 0, 2)  # the plain hgd_spmm_dt, whatever the rule says
+        os.environ["HGD_SPMM_BLOCKS"] = str(args.bf16_blocks)
+        PB = spmm_blocks(S, d, torch.bfloat16) if args.bf16_blocks > 1 else 0
+        os.environ["HGD_SPMM_BLOCKS"] = env_blocks
+        if PB:  # the structure allows blocking: the bf16 hop in PB source blocks
+            variants["bf16_blocked"] = (X16, PB, 2)
 
         def run(key):
             X, blocks, _ = variants[key]
-            return spmm_csr(S, X, val=w, row_scale=q, blocks=blocks)
+            # spmm_csr takes None (the rule or the environment) or 0 (never): a count is forced
+            # through the environment for that call
+            os.environ["HGD_SPMM_BLOCKS"] = str(blocks) if blocks else env_blocks
+            try:
+                return spmm_csr(S, X, val=w, row_scale=q, blocks=None if blocks else blocks)
+            finally:
+                os.environ["HGD_SPMM_BLOCKS"] = env_blocks
 
         ref = run("fp32_plain" if P else "fp32")
         diff = float((run("bf16").float() - ref).abs().max() / ref.abs().max())
@@ -90,7 +107,8 @@ def main():
                 del Y
                 if rnd >= args.warmup:
                     times[key].append(ev[0].elapsed_time(ev[1]) / args.reps)
-        out = {"fp32_blocks": P, "bf16_max_rel_diff_vs_fp32": diff, "variants": {}}
+        out = {"fp32_blocks": P, "bf16_blocks": PB, "bf16_max_rel_diff_vs_fp32": diff,
+               "variants": {}}
         for key, ts in times.items():
             eb = variants[key][2]
             nbytes = profiling.hop_bytes(nnz, R, d, x_bytes=eb, y_bytes=eb)
@@ -106,6 +124,11 @@ def main():
                                                  / v["bf16"]["bytes_algorithmic"], 3)
         print(f"{name:10s} time fp32/bf16 {out['time_ratio_fp32_over_bf16']:.3f}x  "
               f"(bytes {out['byte_ratio_fp32_over_bf16']:.3f}x)", flush=True)
+        if PB:
+            out["time_ratio_fp32_over_bf16_blocked"] = round(
+                v["fp32"]["ms"] / v["bf16_blocked"]["ms"], 3)
+            print(f"{name:10s} time fp32/bf16 blocked (P = {PB}) "
+                  f"{out['time_ratio_fp32_over_bf16_blocked']:.3f}x", flush=True)
         res["hops"][name] = out
         del X32, X16, X32r
     print(json.dumps(res), flush=True)

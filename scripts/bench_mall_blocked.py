@@ -11,7 +11,12 @@ block-major copy of the CSC, hgd_spmm_col_blocks, selected through HGD_SPMM_BLOC
 hgd_spmm in interleaved rounds and reports the worst relative difference (a different fp32
 summation order, so not bitwise).
 
-    python scripts/bench_mall_blocked.py [--dim 64 --rounds 5]
+--table-dtype bf16 times the same over a bfloat16 table (hgd_spmm_dt against hgd_spmm_blocked_dt;
+--out-dtype: the output's type, default the table's): the same interleaved rounds, the median with
+the min–max spread of the rounds, and TB/s on the variant's own algorithmic bytes
+(profiling.hop_bytes with its element sizes).
+
+    python scripts/bench_mall_blocked.py [--dim 64 --rounds 5 --table-dtype bf16]
 """
 import argparse
 import json
@@ -45,12 +50,16 @@ def main():
                     help="HGD_TUNE_SPMM_BLOCKED_SEG for the blocked variants (1 = segmented walk)")
     ap.add_argument("--pass-cols", type=int, default=0,
                     help="HGD_TUNE_SPMM_PASS_COLS for every variant (0 = the default passes)")
+    ap.add_argument("--table-dtype", choices=("f32", "bf16"), default="f32",
+                    help="element type of the gathered table")
+    ap.add_argument("--out-dtype", choices=("f32", "bf16"), default=None,
+                    help="element type of the output (default: the table's)")
     args = ap.parse_args()
 
     import torch
 
     import bench
-    from hypergraph_diffusion_for_recommendation_amd import Incidence
+    from hypergraph_diffusion_for_recommendation_amd import Incidence, profiling
     from hypergraph_diffusion_for_recommendation_amd.incidence import spmm_csr
 
     from hypergraph_diffusion_for_recommendation_amd import _native as nat
@@ -80,6 +89,12 @@ def main():
         X = torch.randn(I, d, device=dev)
         q = inc.scale("row", "sym")
         w_full = None
+    dtypes = {"f32": torch.float32, "bf16": torch.bfloat16}
+    x_dtype = dtypes[args.table_dtype]
+    y_dtype = dtypes[args.out_dtype or args.table_dtype]
+    if x_dtype != torch.float32:
+        # (a column slice stays one: the wide table is converted, then cut again)
+        X = X.to(x_dtype) if X._base is None else X._base.to(x_dtype)[:, :d]
     blocks = [int(p) for p in args.blocks.split(",")]
     for P in blocks:  # block-major copies built outside the timed rounds
         S.col_blocks(P)
@@ -88,11 +103,15 @@ def main():
     def run(P):
         # HGD_SPMM_BLOCKS=0: hgd_spmm; =P: hgd_spmm_blocked over P source ranges (spmm_blocks)
         os.environ["HGD_SPMM_BLOCKS"] = str(P)
-        return spmm_csr(S, X, val=w_full, row_scale=q)
+        return spmm_csr(S, X, val=w_full, row_scale=q, out_dtype=y_dtype)
 
-    ref = run(0)
+    ref = run(0).float()
     res = {"dim": d, "hop": args.hop, "pass_cols": args.pass_cols, "policy": args.policy, "unroll": args.unroll, "seg": args.seg, "ld": args.ld, "nnz": nnz,
-           "bytes_algorithmic": nnz * (4 + 4 * d) + R * (4 * d + 4) + (R + 1) * 4, "variants": {}}
+           "table_dtype": args.table_dtype, "out_dtype": args.out_dtype or args.table_dtype,
+           "rounds": args.rounds,
+           "bytes_algorithmic": profiling.hop_bytes(nnz, R, d, x_bytes=X.element_size(),
+                                                    y_bytes=4 if y_dtype == torch.float32 else 2),
+           "variants": {}}
     times = {"plain": []}
     times.update({P: [] for P in blocks})
     diffs = {}
@@ -106,13 +125,17 @@ def main():
             if rnd:
                 times[key].append(ev[0].elapsed_time(ev[1]))
             elif key != "plain":
-                diffs[key] = float((Y - ref).abs().max() / ref.abs().max())
+                diffs[key] = float((Y.float() - ref).abs().max() / ref.abs().max())
+            del Y
     for key, ts in times.items():
         ms = statistics.median(ts)
-        res["variants"][str(key)] = {"ms": round(ms, 4),
+        res["variants"][str(key)] = {"ms": round(ms, 4), "ms_min": round(min(ts), 4),
+                                     "ms_max": round(max(ts), 4),
                                      "GBps_algorithmic": round(res["bytes_algorithmic"] / ms / 1e6,
                                                                1),
                                      "max_rel_diff_vs_plain": diffs.get(key, 0.0)}
+        print(f"{str(key):6s} {ms:8.3f} ms (min {min(ts):.3f}, max {max(ts):.3f})  "
+              f"{res['bytes_algorithmic'] / ms / 1e9:6.3f} TB/s", flush=True)
     print(json.dumps(res), flush=True)
 
 
