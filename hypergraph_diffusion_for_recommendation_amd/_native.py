@@ -441,6 +441,13 @@ _SIGNATURES = {
     "hgd_conv2hop_backward": (c_i32, [c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_i32,
                                       c_void_p, c_i32, c_f32, c_void_p, c_i64, c_void_p,
                                       c_void_p, c_size, c_void_p]),
+    # KG attention (KHGRec's update_attention)
+    "hgd_kg_attention_scores": (c_i32, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i32,
+                                        c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_i64, c_void_p, c_void_p]),
+    "hgd_kg_attention_softmax_workspace_size": (c_size, [c_i64]),
+    "hgd_kg_attention_softmax": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
+                                         c_void_p, c_void_p, c_size, c_void_p]),
 }
 
 _lib = None

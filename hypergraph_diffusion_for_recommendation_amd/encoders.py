@@ -12,6 +12,8 @@ encoder (paths relative to /root/reference/HD_SELFRec):
 * :class:`SelfAwareEncoder`  model/graph/HGNN_cp.py:368-411, KHGRec.py:374-417 (the KG
   carriers' CF side)
 * :class:`RelationalAwareEncoder` model/graph/HGNN_cp.py:413-446 (their KG side)
+* :class:`KHGRecRelationalAwareEncoder` model/graph/KHGRec.py:419-438 (KHGRec's KG side, with
+  the KG attention of :mod:`.kg_attention`)
 * :class:`SelfAwareEncoderHD` model/graph/HD.py:398-487 (ED-HNN blocks on the norm_adj pattern)
 
 Everything sparse runs on libhgd, with the LayerNorm / residual after a hop fused into its store;
@@ -24,11 +26,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .functional import (dense_two_hop_pair, fan, hccf_layers, hccf_layers_supported,
-                         hyper_dropouts, split_rows, sum_n, table_projections,
-                         two_hop_fused)
+from .functional import (att_two_hop_fused, dense_two_hop_pair, fan, hccf_layers,
+                         hccf_layers_supported, hyper_dropouts, split_rows, sum_n,
+                         table_projections, two_hop_fused)
 from .incidence import Incidence, incidence_of
-from .layers import EquivSetGNN, GCNLayer, HGCNConv, HGNNLayer, LayerNorm, SpAdjDropEdge
+from .layers import (AttHGCNConv, EquivSetGNN, GCNLayer, HGCNConv, HGNNLayer, LayerNorm,
+                     SpAdjDropEdge)
 
 
 def sparse_tensor_of(mat, device) -> torch.Tensor:
@@ -388,8 +391,8 @@ class SelfAwareEncoder(nn.Module):
 class RelationalAwareEncoder(nn.Module):
     """HGNN_cp's KG encoder (HGNN_cp.py:413-446): the same ``lns[i](HGCNConv(A, x)) + res``
     stack over the (edge-dropped) KG adjacency; its AttHGCNConv ignores ``att_adj`` (``adj =
-    inp_adj``, :440-446), as here. (KHGRec's variant multiplies ``att_adj·inp_adj`` first,
-    KHGRec.py:445-449 — a KG-attention SpGEMM outside the path.)"""
+    inp_adj``, :440-446), as here. KHGRec's variant, which does apply ``att_adj``
+    (KHGRec.py:445-449), is :class:`KHGRecRelationalAwareEncoder`."""
 
     def __init__(self, leaky, dropout, n_layers, hyper_dim):
         super().__init__()
@@ -406,6 +409,39 @@ class RelationalAwareEncoder(nn.Module):
     def forward(self, embs, sparse_adj, att_adj=None):
         return _hgcn_ln_res_stack(incidence_of(sparse_adj), embs, list(self.lns),
                                   float(self.leaky), embs)
+
+
+class KHGRecRelationalAwareEncoder(nn.Module):
+    """KHGRec's KG encoder (KHGRec.py:419-438): per layer ``lns[i](AttHGCNConv(A, att, x)) +
+    residual`` with AttHGCNConv = LeakyReLU(adj·adjᵀ·x), adj = att·A (no activation on the last
+    layer). ``sparse_adj`` is the (edge-dropped) KG adjacency; ``att_adj`` the attention matrix
+    of :func:`~.kg_attention.kg_attention` (an Incidence) or a torch sparse tensor such as the
+    reference's initial ``sparse_identity``. Each layer is one fused four-hop
+    (functional.att_two_hop_fused) whose last store applies the LeakyReLU, the LayerNorm and
+    the residual. Same constructor and parameter names (``convs``, ``lns``) as the reference."""
+
+    def __init__(self, leaky, dropout, n_layers, hyper_dim):
+        super().__init__()
+        self.leaky = leaky
+        self.dropout = dropout
+        self.n_layers = n_layers
+        self.convs = nn.ModuleList()
+        self.lns = nn.ModuleList()
+        for _ in range(n_layers):
+            self.convs.append(AttHGCNConv(leaky=leaky))
+            self.lns.append(LayerNorm(hyper_dim))
+
+    def forward(self, embs, sparse_adj, att_adj):
+        inc = incidence_of(sparse_adj)
+        att = incidence_of(att_adj, cache=False)
+        L = self.n_layers
+        uses = fan(embs, L + 1)  # one n-ary gradient sum of the residual (_hgcn_ln_res_stack)
+        x, res = uses[0], uses[1:]
+        for k in range(L):
+            x = att_two_hop_fused(att, inc, x, epilogue=None if k == L - 1 else "leaky_relu",
+                                  slope=float(self.leaky), norm=self.lns[k], res1=res[k],
+                                  res1_scale=1.0)
+        return x
 
 
 class SelfAwareEncoderHD(nn.Module):

@@ -15,6 +15,9 @@ Operators (reference call sites, relative to /root/reference/HD_SELFRec):
                                                   layers2/EquivSetConv2.py:88-93);
                                                   the HGNN normalisation D_v^-1/2 H D_e^-1 Hᵀ D_v^-1/2
                                                   (data/graph.py:28-42) — the benchmarked op.
+* :func:`att_two_hop` ``Y = epi(att·A·Aᵀ·attᵀ·X)``  — AttHGCNConv.forward with the KG attention
+                                                  (model/graph/KHGRec.py:445-453), four hops
+                                                  instead of the reference's SpGEMM att·A.
 
 Scales are named: None, 'mean' (1/deg), 'sym' (deg^-1/2), or the weighted 'wmean'/'wsym'.
 The math of the backward: with Z = P·A·Q·Aᵀ·R·X, dX = R·A·Q·Aᵀ·P·dZ (the diagonals commute
@@ -288,6 +291,166 @@ def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
     cfg = (P, Q, R, epi, float(slope), ln, float(norm.eps) if ln else 0.0, float(out_scale),
            float(res1_scale), float(res2_scale))
     return _FusedTwoHop.apply(X, gamma, beta, res1, res2, inc, cfg)
+
+
+def _att_hops(att: Incidence, inc: Incidence, X: torch.Tensor):
+    """``K·(Kᵀ·(attᵀ·X))``: the first three of the four hops of ``adj·(adjᵀ·X)``, adj = att·K."""
+    T = spmm_csr(att.csc, X, val=att.val_t)
+    M = spmm_csr(inc.csc, T, val=inc.val_t)
+    return spmm_csr(inc.csr, M, val=inc.val)
+
+
+def _check_att(att: Incidence, inc: Incidence, X: torch.Tensor, what: str) -> None:
+    if X.dtype != torch.float32:
+        raise TypeError(f"{what}: float32 only, got {X.dtype}")
+    if att.n_cols != inc.n_rows:
+        raise ValueError(f"{what}: att is {att.shape}, the adjacency {inc.shape}")
+    if X.dim() != 2 or X.shape[0] != att.n_rows:
+        raise ValueError(f"{what}: X {tuple(X.shape)} for an att of {att.shape}")
+
+
+class _AttTwoHop(torch.autograd.Function):
+    """``Y = epi(att·K·Kᵀ·attᵀ·X)`` as four hops, the activation in the last hop's store. The
+    operator is symmetric, so the backward is the same four hops over ``epi'(dY)``. Gradient
+    through ``X`` only: the attention carries none (KHGRec.py:331 assigns ``.data``)."""
+
+    @staticmethod
+    def forward(ctx, X, att: Incidence, inc: Incidence, epi: int, slope: float):
+        Z = _att_hops(att, inc, X.contiguous())
+        fuse = epi != nat.EPI_NONE and slope >= 0.0
+        Y = spmm_csr(att.csr, Z, val=att.val, epilogue=epi if fuse else 0, slope=slope)
+        ref = Y
+        if epi != nat.EPI_NONE and not fuse:
+            Y = _epilogue_apply(ref, epi, slope)
+        ctx.att, ctx.inc, ctx.epi, ctx.slope = att, inc, epi, slope
+        if epi != nat.EPI_NONE:
+            ctx.save_for_backward(ref)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        dZ = dY.contiguous()
+        if ctx.epi != nat.EPI_NONE:
+            (ref,) = ctx.saved_tensors
+            dZ = _epilogue_backward(ref, dZ, ctx.epi, ctx.slope)
+        dX = spmm_csr(ctx.att.csr, _att_hops(ctx.att, ctx.inc, dZ), val=ctx.att.val)
+        return dX, None, None, None, None
+
+
+def att_two_hop(att: Incidence, inc: Incidence, X: torch.Tensor, epilogue: Optional[str] = None,
+                slope: float = 0.0) -> torch.Tensor:
+    """``epi(adj·(adjᵀ·X))`` with ``adj = att·K`` (AttHGCNConv.forward, KHGRec.py:445-453) as the
+    four hops ``att·(K·(Kᵀ·(attᵀ·X)))``: no sparse × sparse product and none of its fill-in.
+    ``att`` [n, m] and ``inc`` = K [m, c] are Incidences (``inc`` may be an edge-dropped view);
+    ``X`` is float32 [n, d]. Autograd through ``X`` only."""
+    _check_att(att, inc, X, "att_two_hop")
+    return _AttTwoHop.apply(X, att, inc, _EPI[epilogue], float(slope))
+
+
+class _FusedAttTwoHop(torch.autograd.Function):
+    """``Y = out_scale·LN(epi(att·K·Kᵀ·attᵀ·X)) + s1·res1 + s2·res2`` — :class:`_FusedTwoHop`
+    over the four hops of :func:`att_two_hop`: the last hop's store runs the activation,
+    LayerNorm and residual blend, the backward their gradient in one pass before four hops."""
+
+    @staticmethod
+    def forward(ctx, X, gamma, beta, res1, res2, att: Incidence, inc: Incidence, cfg):
+        epi, slope, ln, eps, out_scale, s1, s2 = cfg
+        dev = X.device
+        n, d = att.n_rows, X.shape[1]
+        Z = _att_hops(att, inc, X.contiguous())
+        need_a = ln or epi != nat.EPI_NONE
+        A = torch.empty((n, d), dtype=torch.float32, device=dev) if need_a else None
+        stats = torch.empty((n, 2), dtype=torch.float32, device=dev) if ln else None
+        res1 = None if res1 is None else res1.contiguous()
+        res2 = None if res2 is None else res2.contiguous()
+        ex = nat.RowEpilogue(
+            act=epi, slope=slope, layer_norm=int(ln), ln_eps=eps,
+            ln_gamma=nat.ptr(gamma) if ln else None, ln_beta=nat.ptr(beta) if ln else None,
+            out_scale=out_scale,
+            res1=nat.ptr(res1), ld_res1=0 if res1 is None else res1.stride(0), res1_scale=s1,
+            res2=nat.ptr(res2), ld_res2=0 if res2 is None else res2.stride(0), res2_scale=s2,
+            act_out=nat.ptr(A), ld_act=0 if A is None else A.stride(0), stats=nat.ptr(stats))
+        Y = spmm_csr(att.csr, Z, val=att.val, ex=ex)
+        ctx.att, ctx.inc, ctx.cfg = att, inc, cfg
+        ctx.has_res = (res1 is not None, res2 is not None)
+        ctx.save_for_backward(A, stats, gamma if ln else None)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        att, inc = ctx.att, ctx.inc
+        epi, slope, ln, eps, out_scale, s1, s2 = ctx.cfg
+        A, stats, gamma = ctx.saved_tensors
+        dY = dY.contiguous()
+        n, d = dY.shape
+        dev = dY.device
+        dgamma = dbeta = None
+        if not ln and epi == nat.EPI_NONE:
+            dZ = dY if out_scale == 1.0 else dY * out_scale  # a pure blend
+        else:
+            want_g = ln and ctx.needs_input_grad[1]
+            want_b = ln and ctx.needs_input_grad[2]
+            dgamma = torch.empty(d, dtype=torch.float32, device=dev) if want_g else None
+            dbeta = torch.empty(d, dtype=torch.float32, device=dev) if want_b else None
+            lib = nat.load()
+            wsb = (lib.hgd_row_epilogue_backward_workspace_size(n, d)
+                   if (want_g or want_b) else 0)
+            ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev) if wsb else None
+            dZ = torch.empty_like(dY)
+            nat.check(lib.hgd_row_epilogue_backward(
+                dY.data_ptr(), dY.stride(0), nat.ptr(A), 0 if A is None else A.stride(0),
+                nat.ptr(stats), nat.ptr(gamma), n, d, epi, float(slope), int(ln),
+                float(out_scale), dZ.data_ptr(), dZ.stride(0), nat.ptr(dgamma), nat.ptr(dbeta),
+                nat.ptr(ws), wsb, nat.stream_handle(dev)), "hgd_row_epilogue_backward")
+        dX = None
+        if ctx.needs_input_grad[0]:
+            dX = spmm_csr(att.csr, _att_hops(att, inc, dZ), val=att.val)
+        return (dX, dgamma, dbeta, _res_grad(ctx, dY, 0, s1), _res_grad(ctx, dY, 1, s2), None,
+                None, None)
+
+
+def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
+                      epilogue: Optional[str] = None, slope: float = 0.0,
+                      norm: Optional[torch.nn.LayerNorm] = None, out_scale: float = 1.0,
+                      res1: Optional[torch.Tensor] = None, res1_scale: float = 1.0,
+                      res2: Optional[torch.Tensor] = None,
+                      res2_scale: float = 1.0) -> torch.Tensor:
+    """``out_scale·norm(epi(att·K·Kᵀ·attᵀ·X)) + res1_scale·res1 + res2_scale·res2`` with
+    autograd: :func:`att_two_hop` with the last hop's store running the fused row epilogue, as
+    :func:`two_hop_fused` does for the bare two-hop (one layer of KHGRec's
+    RelationalAwareEncoder, KHGRec.py:431-438). A row of ``att`` without entries gives z = 0,
+    so LayerNorm yields β and the row is β plus the residual, as in the reference. Shapes the
+    fused store cannot hold (LayerNorm with d > 256, or a negative slope) run the same math as
+    separate device ops."""
+    _check_att(att, inc, X, "att_two_hop_fused")
+    epi = _EPI[epilogue]
+    for t in (res1, res2):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"att_two_hop_fused: float32 only, got {t.dtype}")
+    d = X.shape[1]
+    ln = norm is not None
+    if ln and (tuple(norm.normalized_shape) != (d,)):
+        raise ValueError(f"att_two_hop_fused: LayerNorm over {tuple(norm.normalized_shape)}, "
+                         f"d={d}")
+    for r in (res1, res2):
+        if r is not None and tuple(r.shape) != (att.n_rows, d):
+            raise ValueError(f"att_two_hop_fused: residual {tuple(r.shape)} != "
+                             f"{(att.n_rows, d)}")
+    if (ln and not _ln_supported(d)) or (epi != nat.EPI_NONE and slope < 0):
+        y = att_two_hop(att, inc, X, epilogue=epilogue, slope=slope)
+        if ln:
+            y = norm(y)
+        y = out_scale * y
+        if res1 is not None:
+            y = y + res1_scale * res1
+        if res2 is not None:
+            y = y + res2_scale * res2
+        return y
+    gamma = norm.weight if ln and norm.weight is not None else None
+    beta = norm.bias if ln and norm.bias is not None else None
+    cfg = (epi, float(slope), ln, float(norm.eps) if ln else 0.0, float(out_scale),
+           float(res1_scale), float(res2_scale))
+    return _FusedAttTwoHop.apply(X, gamma, beta, res1, res2, att, inc, cfg)
 
 
 def _linear_native_ok(X: torch.Tensor, weight: torch.Tensor) -> bool:

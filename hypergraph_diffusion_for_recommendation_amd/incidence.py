@@ -295,6 +295,11 @@ def spmm_row_order(csr: CSR, d: int) -> bool:
     wherever it applies, unset (or ``auto``) = the size rule."""
     if csr.n_heavy or csr.segmented or csr.nnz == 0:
         return False
+    if not getattr(csr, "row_order_ok", True):
+        # a structure that opted out (a KG attention pattern: rebuilt per batch, few entries in
+        # many rows, and its arrays may run past rowptr[n_rows], which the order's gather
+        # permutation does not cover) — not even when the environment forces the order
+        return False
     env = os.environ.get("HGD_SPMM_ROW_ORDER", "")
     if env not in ("", "auto"):
         if env not in ("0", "1"):

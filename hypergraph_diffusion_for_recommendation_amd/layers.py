@@ -11,6 +11,7 @@ class                  reference                                        hot op h
 GCNLayer               model/graph/HCCF.py:193-199                      hgd_spmm (CSR, + CSC bwd)
 HGNNLayer              model/graph/HCCF.py:201-211                      hgd_linear_* (f32 MFMA)
 HGCNConv               model/graph/HGNN_HD4.py:450-462 (and copies)     2 hops, fused LeakyReLU
+AttHGCNConv            model/graph/KHGRec.py:440-453                    4 hops, fused LeakyReLU
 SpAdjDropEdge          model/graph/HCCF.py:213-226                      hgd_dropedge_compact
 EquivSetConv           model/layers/layers2/EquivSetConv2.py:38-100     mean/sum 2-hop (V/E)
 EquivSetGNN            model/layers/layers2/EquivSetGNN2.py:32-155      hgd_dense_threshold_*
@@ -32,7 +33,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .functional import (dense_mean_two_hop, dense_mean_two_hop_ok,
+from .functional import (att_two_hop, dense_mean_two_hop, dense_mean_two_hop_ok,
                          dense_mean_two_hop_pair, dense_two_hop,
                          dropout_seed, layer_norm, linear, linear_relu_dropout, spmm, two_hop,
                          two_hop_fused)
@@ -78,6 +79,31 @@ class HGCNConv(nn.Module):
         if act:
             return two_hop(inc, embs, epilogue="leaky_relu", slope=self.act.negative_slope)
         return two_hop(inc, embs)
+
+
+class AttHGCNConv(nn.Module):
+    """KHGRec's attention conv (KHGRec.py:440-453): ``adj = att_adj·inp_adj`` and then
+    ``leaky(adj·(adjᵀ·X))`` or ``adj·(adjᵀ·X)``. The reference forms ``adj`` with a sparse ×
+    sparse product in every layer; here the same map runs as four hops,
+    ``att·(K·(Kᵀ·(attᵀ·X)))`` (functional.att_two_hop), with neither the product nor its fill-in.
+
+    ``inp_adj``: an Incidence, a torch sparse COO tensor or an edge-dropped view, as HGCNConv
+    takes them. ``att_adj``: the Incidence of ``kg_attention`` / ``KGAttentionPattern.update``,
+    or a torch sparse COO tensor such as the ``sparse_identity`` the reference starts with (its
+    structure is rebuilt on every call, because the reference replaces that tensor's ``.data``
+    in place). Gradient flows through ``embs`` only."""
+
+    def __init__(self, leaky):
+        super().__init__()
+        self.act = nn.LeakyReLU(negative_slope=leaky)
+
+    def forward(self, inp_adj, att_adj, embs, act=True):
+        inc = incidence_of(inp_adj)
+        att = incidence_of(att_adj, cache=False)
+        if act:
+            return att_two_hop(att, inc, embs, epilogue="leaky_relu",
+                               slope=self.act.negative_slope)
+        return att_two_hop(att, inc, embs)
 
 
 _NATIVE_CPU_MASK: Optional[bool] = None

@@ -25,6 +25,9 @@
  *   hgd_dropedge_compact     SpAdjDropEdge.forward, model/graph/HCCF.py:213-226 (vals[mask]/keep, idxs[:,mask])
  *   hgd_dense_threshold_*    torch.nonzero(hypergraph > 0), model/layers/layers2/EquivSetGNN2.py:105-133
  *                            (row-major order identical to torch.nonzero)
+ *   hgd_kg_attention_scores  update_attention_batch and its per-relation loop,
+ *                            model/graph/KHGRec.py:298-320
+ *   hgd_kg_attention_softmax torch.sparse.softmax(A_in.cpu(), dim=1), KHGRec.py:326-331
  *
  * Conventions:
  *   - All pointers are DEVICE pointers unless a parameter says "host".
@@ -1183,6 +1186,55 @@ hgd_status hgd_conv2hop_backward(const hgd_incidence* inc, int32_t P, int32_t Q,
                                  int32_t epilogue, float slope, float* dX, int64_t ldx,
                                  hgd_comm* comm, void* workspace, size_t workspace_bytes,
                                  void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * KG attention: KHGRec's update_attention (model/graph/KHGRec.py:298-331, called on every
+ * minibatch, :122) for a batch of B triples (h, t, r) without leaving the device. fp32, every
+ * sum in a fixed order, no atomics: two runs are bitwise equal, and a triple's score does not
+ * depend on its position in the batch.
+ *
+ * hgd_kg_attention_scores — Equation 4, update_attention_batch (KHGRec.py:298-307) and the
+ * per-relation loop around it (:312-320: one torch.where, two gathers and two matmuls per
+ * relation) as ONE launch:
+ *   v[i] = Σ_k (E[t_i]·W_r)_k · tanh((E[h_i]·W_r)_k + R[r]_k),  r = r_i
+ *   E: [n_ent, d] rows ldE apart; W: [n_rel, d, dr] contiguous (trans_M); R: [n_rel, dr] rows ldR
+ *   apart (relation_emb); h, t: int32 [B] in the batch's order.
+ *   grp_perm: int32 [B], the triples grouped by relation (hgd_sort_perm of r: position p of the
+ *   grouped order is triple grp_perm[p]); rel_off: int64 [n_rel+1], relation r owns positions
+ *   [rel_off[r], rel_off[r+1]) (hgd_rowptr_from_sorted). A workgroup takes 32 triples of one
+ *   relation and reads W_r once, into LDS when d·dr·4 bytes fit beside the staged rows (30 KB),
+ *   through the cache otherwise; an empty relation gets no workgroup.
+ *   rel_enable: uint8 [n_rel] or NULL, the `relations` argument of update_attention: v of a
+ *   disabled relation's triples is not written.
+ *   v: fp32 [B] in the batch's order. B = 0 launches nothing.
+ *
+ * hgd_kg_attention_softmax — Equation 5, torch.sparse.softmax(A_in.cpu(), dim=1) (KHGRec.py:326-
+ * 331) over the UNCOALESCED batch at its fixed size: the entries of the [n_rows, n_rows] matrix
+ * stay B, sorted by (row, column), and torch's coalesce-then-softmax becomes
+ *   val[p] = exp(s − m)/Z for the first entry of a run of equal (row, column), s = the run's sum
+ *            of v taken in the run's order, m and Z the row's max and Σ exp(s − m) over its runs;
+ *   val[p] = 0 for the run's other entries — the same linear map as the coalesced matrix.
+ *   rowptr: int64 [n_rows+1] and col: int32 [B], the sorted entries as a CSR; perm: int32 [B],
+ *   entry p is triple perm[p] (v is read through it). rowptr[n_rows] may be below B: the entries
+ *   past it (triples of disabled relations, sorted behind the last row) get val = 0. A row
+ *   without entries is an empty row; nothing is written for it.
+ *   A workgroup owns 256 rows: a row of up to 8 entries is done by one lane, up to 512 by a
+ *   wave, a longer one by the whole workgroup (a row may be the whole batch), so a long row
+ *   does not serialise on one lane. The limit of that: a RUN's sum is taken in order by the one
+ *   worker that owns the run's first entry, so a row whose entries all repeat one (row, column)
+ *   — up to the whole batch — is summed by a single lane, whichever form takes the row.
+ *   Workspace: hgd_kg_attention_softmax_workspace_size (the runs' sums and exponentials, so that
+ *   val is written once). Stream-ordered, no host synchronisation. */
+hgd_status hgd_kg_attention_scores(const float* E, int64_t ldE, int64_t n_ent, const float* W,
+                                   const float* R, int64_t ldR, int32_t n_rel, int32_t d,
+                                   int32_t dr, const int32_t* h, const int32_t* t,
+                                   const int32_t* grp_perm, const int64_t* rel_off,
+                                   const uint8_t* rel_enable, int64_t B, float* v, void* stream);
+size_t hgd_kg_attention_softmax_workspace_size(int64_t B);
+hgd_status hgd_kg_attention_softmax(const int64_t* rowptr, const int32_t* col,
+                                    const int32_t* perm, int64_t n_rows, int64_t B,
+                                    const float* v, float* val, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,30 @@ def hgcn_conv(adj, X, act=True, slope=0.5):
     return F.leaky_relu(Y, slope) if act else Y
 
 
+def update_attention(E, heads, tails, rels, relations, trans_M, relation_emb, shape):
+    """What KHGRec's update_attention computes per minibatch (KHGRec.py:298-331), with the same
+    torch ops in the same places: per relation one torch.where, two row gathers and two matmuls
+    for the Equation 4 scores; one uncoalesced COO over all of them; Equation 5 as
+    torch.sparse.softmax on the CPU, and the copy back to the device."""
+    idx, score = [], []
+    for q in relations:
+        sel = torch.where(rels == q)
+        hq, tq = heads[sel], tails[sel]
+        proj_h = torch.matmul(E[hq], trans_M[q])
+        proj_t = torch.matmul(E[tq], trans_M[q])
+        score.append((proj_t * torch.tanh(proj_h + relation_emb[q])).sum(dim=1))
+        idx.append(torch.stack([hq, tq]))
+    att = torch.sparse_coo_tensor(torch.cat(idx, dim=1), torch.cat(score), torch.Size(shape))
+    return torch.sparse.softmax(att.cpu(), dim=1).to(E.device)
+
+
+def att_hgcn_conv(inp_adj, att_adj, embs, act=True, slope=0.5):
+    """AttHGCNConv.forward (KHGRec.py:445-453): the sparse × sparse product, then the two hops."""
+    adj = torch.sparse.mm(att_adj, inp_adj)
+    Y = torch.sparse.mm(adj, torch.sparse.mm(adj.t(), embs))
+    return F.leaky_relu(Y, slope) if act else Y
+
+
 def contrast_loss(embeds1, embeds2, nodes, temp):
     """contrastLoss (util/loss_torch.py:103-110)."""
     embeds1 = F.normalize(embeds1 + 1e-8, p=2)
