@@ -170,62 +170,96 @@ def _ln_supported(d: int) -> bool:
     return d <= 256 if d % 4 == 0 else d <= 64
 
 
-class _FusedTwoHop(torch.autograd.Function):
-    """``Y = out_scale·LN(epi(P·A·Q·Aᵀ·R·X)) + s1·res1 + s2·res2`` — the second hop's store runs
-    the activation, LayerNorm and residual blend (hgd_spmm_fused); the backward runs their
-    gradient in one pass (hgd_row_epilogue_backward) before the two backward hops."""
+# ---- the fused row epilogue out_scale·LN(act(Z)) + s1·res1 + s2·res2: its host protocol --------
+# On the device it is the store of hgd_spmm_fused (or hgd_row_epilogue_forward over an existing
+# Z) and hgd_row_epilogue_backward. Every autograd Function over it takes (Z's source, gamma,
+# beta, res1, res2, ...) in this order: the backward reads needs_input_grad[1..4] for them.
 
-    @staticmethod
-    def forward(ctx, X, gamma, beta, res1, res2, inc: Incidence, cfg):
-        P, Q, R, epi, slope, ln, eps, out_scale, s1, s2 = cfg
-        X = X.contiguous()
-        dev = X.device
-        n, d = inc.n_rows, X.shape[1]
-        q = inc.scale("col", Q)
-        M = spmm_csr(inc.csc, X, val=inc.edge_values("csc", R), row_scale=q)
-        p = inc.scale("row", P)
-        need_a = ln or epi != nat.EPI_NONE
-        A = torch.empty((n, d), dtype=torch.float32, device=dev) if need_a else None
-        stats = torch.empty((n, 2), dtype=torch.float32, device=dev) if ln else None
-        res1 = None if res1 is None else res1.contiguous()
-        res2 = None if res2 is None else res2.contiguous()
-        ex = nat.RowEpilogue(
+
+def _row_epilogue_cfg(what: str, n_rows: int, d: int, epilogue, slope, norm, out_scale, res1,
+                      res1_scale, res2, res2_scale):
+    """Checks the epilogue's arguments for the operator ``what`` over [n_rows, d] rows (the
+    LayerNorm's and the residuals' shapes; an operator that rejects 16-bit tensors does so
+    itself, in its own words) and returns ``gamma, beta, cfg, fusable``:
+    ``cfg = (epi, slope, ln, eps, out_scale, s1, s2)``, and whether the fused store can hold the
+    row (LayerNorm needs a row in one lane group, an activation slope >= 0)."""
+    epi = _EPI[epilogue]
+    ln = norm is not None
+    if ln and tuple(norm.normalized_shape) != (d,):
+        raise ValueError(f"{what}: LayerNorm over {tuple(norm.normalized_shape)}, d={d}")
+    for r in (res1, res2):
+        if r is not None and tuple(r.shape) != (n_rows, d):
+            raise ValueError(f"{what}: residual {tuple(r.shape)} != {(n_rows, d)}")
+    gamma = norm.weight if ln and norm.weight is not None else None
+    beta = norm.bias if ln and norm.bias is not None else None
+    cfg = (epi, float(slope), ln, float(norm.eps) if ln else 0.0, float(out_scale),
+           float(res1_scale), float(res2_scale))
+    fusable = not ((ln and not _ln_supported(d)) or (epi != nat.EPI_NONE and slope < 0))
+    return gamma, beta, cfg, fusable
+
+
+def _row_epilogue_setup(ctx, n: int, d: int, dev, gamma, beta, res1, res2, cfg, alias=None):
+    """The forward's side of the protocol: allocates ``act_out`` (act(Z), which the backward
+    reads; without an activation it is Z, and a caller that keeps Z passes it as ``alias``
+    instead of having it written) and the LayerNorm ``stats``, makes the residuals contiguous
+    and records on ``ctx`` what :func:`_row_epilogue_backward` needs. Returns ``ex(r0=0)``, the
+    maker of the descriptor for rows r0, r0+1, … of the [n, d] result."""
+    epi, slope, ln, eps, out_scale, s1, s2 = cfg
+    A = None
+    if ln or epi != nat.EPI_NONE:
+        A = (alias if alias is not None and epi == nat.EPI_NONE
+             else torch.empty((n, d), dtype=torch.float32, device=dev))
+    stats = torch.empty((n, 2), dtype=torch.float32, device=dev) if ln else None
+    res1 = None if res1 is None else res1.contiguous()
+    res2 = None if res2 is None else res2.contiguous()
+    ctx.cfg = cfg
+    ctx.has_res = (res1 is not None, res2 is not None)
+    ctx.save_for_backward(A, stats, gamma if ln else None)
+
+    p1, ld1 = nat.ptr(res1), 0 if res1 is None else res1.stride(0)
+    p2, ld2 = nat.ptr(res2), 0 if res2 is None else res2.stride(0)
+    pa, lda = None if A is alias else nat.ptr(A), 0 if A is None else A.stride(0)
+    ps = nat.ptr(stats)
+
+    def ex(r0=0):
+        o = 4 * r0  # row r0 of a float32 matrix of leading dimension ld: o·ld bytes in
+        return nat.RowEpilogue(
             act=epi, slope=slope, layer_norm=int(ln), ln_eps=eps,
             ln_gamma=nat.ptr(gamma) if ln else None, ln_beta=nat.ptr(beta) if ln else None,
             out_scale=out_scale,
-            res1=nat.ptr(res1), ld_res1=0 if res1 is None else res1.stride(0), res1_scale=s1,
-            res2=nat.ptr(res2), ld_res2=0 if res2 is None else res2.stride(0), res2_scale=s2,
-            act_out=nat.ptr(A), ld_act=0 if A is None else A.stride(0), stats=nat.ptr(stats))
-        Y = spmm_csr(inc.csr, M, val=inc.val, row_scale=p, ex=ex)
-        ctx.inc = inc
-        ctx.cfg = cfg
-        ctx.has_res = (res1 is not None, res2 is not None)
-        ctx.save_for_backward(A, stats, gamma if ln else None)
-        return Y
+            res1=None if p1 is None else p1 + o * ld1, ld_res1=ld1, res1_scale=s1,
+            res2=None if p2 is None else p2 + o * ld2, ld_res2=ld2, res2_scale=s2,
+            act_out=None if pa is None else pa + o * lda, ld_act=lda,
+            stats=None if ps is None else ps + o * 2)
 
-    @staticmethod
-    def backward(ctx, dY):
-        inc = ctx.inc
-        P, Q, R, epi, slope, ln, eps, out_scale, s1, s2 = ctx.cfg
-        A, stats, gamma = ctx.saved_tensors
-        dY = dY.contiguous()
-        n, d = dY.shape
-        dev = dY.device
-        want_g = ln and ctx.needs_input_grad[1]
-        want_b = ln and ctx.needs_input_grad[2]
-        if not ln and epi == nat.EPI_NONE:
-            # a pure blend: dZ = out_scale·dY, folded into the item-side row scale of the first
-            # backward hop (n_cols multiplies instead of an [n, d] pass)
-            dX = None
-            if ctx.needs_input_grad[0]:
-                q = inc.scale("col", Q)
-                if out_scale != 1.0:
-                    q = (torch.full((inc.n_cols,), out_scale, dtype=torch.float32, device=dev)
-                         if q is None else q * out_scale)
-                dM = spmm_csr(inc.csc, dY, val=inc.edge_values("csc", P), row_scale=q)
-                dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=inc.scale("row", R))
-            return (dX, None, None, _res_grad(ctx, dY, 0, s1), _res_grad(ctx, dY, 1, s2), None,
-                    None)
+    return ex
+
+
+def _row_epilogue_forward(Z: torch.Tensor, ex, Y: torch.Tensor) -> None:
+    """``Y = epilogue(Z)`` over an existing matrix (hgd_row_epilogue_forward)."""
+    n, d = Z.shape
+    nat.check(nat.load().hgd_row_epilogue_forward(
+        Z.data_ptr(), Z.stride(0), n, d, ctypes.byref(ex), Y.data_ptr(), Y.stride(0),
+        nat.stream_handle(Z.device)), "hgd_row_epilogue_forward")
+
+
+def _row_epilogue_backward(ctx, dY: torch.Tensor, need_dz: bool):
+    """``dZ, dz_scale, dgamma, dbeta, dres1, dres2`` from a contiguous ``dY``. The gradient of
+    Z is ``dz_scale·dZ``: 1 wherever hgd_row_epilogue_backward ran, which is only when dZ
+    (``need_dz``), dγ or dβ is needed; a pure blend (no LayerNorm, no activation) launches
+    nothing and hands back ``dY`` with the pending factor ``out_scale``, which the operator
+    applies where it is cheapest for it."""
+    epi, slope, ln, eps, out_scale, s1, s2 = ctx.cfg
+    A, stats, gamma = ctx.saved_tensors
+    n, d = dY.shape
+    dev = dY.device
+    want_g = ln and ctx.needs_input_grad[1]
+    want_b = ln and ctx.needs_input_grad[2]
+    dZ = dgamma = dbeta = None
+    dz_scale = 1.0
+    if not ln and epi == nat.EPI_NONE:
+        dZ, dz_scale = dY, out_scale
+    elif need_dz or want_g or want_b:
         dgamma = torch.empty(d, dtype=torch.float32, device=dev) if want_g else None
         dbeta = torch.empty(d, dtype=torch.float32, device=dev) if want_b else None
         lib = nat.load()
@@ -234,22 +268,64 @@ class _FusedTwoHop(torch.autograd.Function):
         dZ = torch.empty_like(dY)
         nat.check(lib.hgd_row_epilogue_backward(
             dY.data_ptr(), dY.stride(0), nat.ptr(A), 0 if A is None else A.stride(0),
-            nat.ptr(stats), nat.ptr(gamma), n, d, epi, float(slope), int(ln), float(out_scale),
+            nat.ptr(stats), nat.ptr(gamma), n, d, epi, slope, int(ln), out_scale,
             dZ.data_ptr(), dZ.stride(0), nat.ptr(dgamma), nat.ptr(dbeta), nat.ptr(ws), wsb,
             nat.stream_handle(dev)), "hgd_row_epilogue_backward")
-        dX = None
-        if ctx.needs_input_grad[0]:
-            q = inc.scale("col", Q)
-            dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q)
-            dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=inc.scale("row", R))
-        return (dX, dgamma, dbeta, _res_grad(ctx, dY, 0, s1), _res_grad(ctx, dY, 1, s2), None,
-                None)
+    return dZ, dz_scale, dgamma, dbeta, _res_grad(ctx, dY, 0, s1), _res_grad(ctx, dY, 1, s2)
 
 
 def _res_grad(ctx, dY, k, s):
     if not ctx.has_res[k] or not ctx.needs_input_grad[3 + k]:
         return None
     return dY if s == 1.0 else dY * s
+
+
+def _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale):
+    """The epilogue after its activation as separate device ops, for rows the fused store
+    cannot hold."""
+    if norm is not None:
+        y = norm(y)
+    y = out_scale * y
+    if res1 is not None:
+        y = y + res1_scale * res1
+    if res2 is not None:
+        y = y + res2_scale * res2
+    return y
+
+
+class _FusedTwoHop(torch.autograd.Function):
+    """``Y = out_scale·LN(epi(P·A·Q·Aᵀ·R·X)) + s1·res1 + s2·res2`` — the second hop's store runs
+    the activation, LayerNorm and residual blend (hgd_spmm_fused); the backward runs their
+    gradient in one pass (hgd_row_epilogue_backward) before the two backward hops."""
+
+    @staticmethod
+    def forward(ctx, X, gamma, beta, res1, res2, inc: Incidence, scales, cfg):
+        P, Q, R = scales
+        X = X.contiguous()
+        M = spmm_csr(inc.csc, X, val=inc.edge_values("csc", R), row_scale=inc.scale("col", Q))
+        ex = _row_epilogue_setup(ctx, inc.n_rows, X.shape[1], X.device, gamma, beta, res1, res2,
+                                 cfg)
+        ctx.inc, ctx.scales = inc, scales
+        return spmm_csr(inc.csr, M, val=inc.val, row_scale=inc.scale("row", P), ex=ex())
+
+    @staticmethod
+    def backward(ctx, dY):
+        inc = ctx.inc
+        P, Q, R = ctx.scales
+        need_dx = ctx.needs_input_grad[0]
+        dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
+            ctx, dY.contiguous(), need_dx)
+        dX = None
+        if need_dx:
+            q = inc.scale("col", Q)
+            if dz_scale != 1.0:
+                # a pure blend: dZ = out_scale·dY, folded into the item-side row scale of the
+                # first backward hop (n_cols multiplies instead of an [n, d] pass)
+                q = (torch.full((inc.n_cols,), dz_scale, dtype=torch.float32, device=dZ.device)
+                     if q is None else q * dz_scale)
+            dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q)
+            dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=inc.scale("row", R))
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None
 
 
 def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
@@ -264,33 +340,17 @@ def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
     restart blend kernels. ``norm`` is an ``nn.LayerNorm`` over the last
     dim (its weight/bias get gradients). Shapes the fused store cannot hold (LayerNorm with
     d > 256, or a negative slope) run the same math as separate device ops."""
-    epi = _EPI[epilogue]
     for t in (X, res1, res2):
         if t is not None and t.dtype != torch.float32:
             raise TypeError(f"two_hop_fused: float32 only (the fused row epilogue has no 16-bit "
                             f"form), got {t.dtype}; use two_hop for a bfloat16 table")
-    d = X.shape[1]
-    ln = norm is not None
-    if ln and (tuple(norm.normalized_shape) != (d,)):
-        raise ValueError(f"two_hop_fused: LayerNorm over {tuple(norm.normalized_shape)}, d={d}")
-    for r in (res1, res2):
-        if r is not None and tuple(r.shape) != (inc.n_rows, d):
-            raise ValueError(f"two_hop_fused: residual {tuple(r.shape)} != {(inc.n_rows, d)}")
-    if (ln and not _ln_supported(d)) or (epi != nat.EPI_NONE and slope < 0):
+    gamma, beta, cfg, fusable = _row_epilogue_cfg(
+        "two_hop_fused", inc.n_rows, X.shape[1], epilogue, slope, norm, out_scale, res1,
+        res1_scale, res2, res2_scale)
+    if not fusable:
         y = two_hop(inc, X, P=P, Q=Q, R=R, epilogue=epilogue, slope=slope)
-        if ln:
-            y = norm(y)
-        y = out_scale * y
-        if res1 is not None:
-            y = y + res1_scale * res1
-        if res2 is not None:
-            y = y + res2_scale * res2
-        return y
-    gamma = norm.weight if ln and norm.weight is not None else None
-    beta = norm.bias if ln and norm.bias is not None else None
-    cfg = (P, Q, R, epi, float(slope), ln, float(norm.eps) if ln else 0.0, float(out_scale),
-           float(res1_scale), float(res2_scale))
-    return _FusedTwoHop.apply(X, gamma, beta, res1, res2, inc, cfg)
+        return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
+    return _FusedTwoHop.apply(X, gamma, beta, res1, res2, inc, (P, Q, R), cfg)
 
 
 def _att_hops(att: Incidence, inc: Incidence, X: torch.Tensor):
@@ -354,59 +414,24 @@ class _FusedAttTwoHop(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, gamma, beta, res1, res2, att: Incidence, inc: Incidence, cfg):
-        epi, slope, ln, eps, out_scale, s1, s2 = cfg
-        dev = X.device
-        n, d = att.n_rows, X.shape[1]
         Z = _att_hops(att, inc, X.contiguous())
-        need_a = ln or epi != nat.EPI_NONE
-        A = torch.empty((n, d), dtype=torch.float32, device=dev) if need_a else None
-        stats = torch.empty((n, 2), dtype=torch.float32, device=dev) if ln else None
-        res1 = None if res1 is None else res1.contiguous()
-        res2 = None if res2 is None else res2.contiguous()
-        ex = nat.RowEpilogue(
-            act=epi, slope=slope, layer_norm=int(ln), ln_eps=eps,
-            ln_gamma=nat.ptr(gamma) if ln else None, ln_beta=nat.ptr(beta) if ln else None,
-            out_scale=out_scale,
-            res1=nat.ptr(res1), ld_res1=0 if res1 is None else res1.stride(0), res1_scale=s1,
-            res2=nat.ptr(res2), ld_res2=0 if res2 is None else res2.stride(0), res2_scale=s2,
-            act_out=nat.ptr(A), ld_act=0 if A is None else A.stride(0), stats=nat.ptr(stats))
-        Y = spmm_csr(att.csr, Z, val=att.val, ex=ex)
-        ctx.att, ctx.inc, ctx.cfg = att, inc, cfg
-        ctx.has_res = (res1 is not None, res2 is not None)
-        ctx.save_for_backward(A, stats, gamma if ln else None)
-        return Y
+        ex = _row_epilogue_setup(ctx, att.n_rows, X.shape[1], X.device, gamma, beta, res1, res2,
+                                 cfg)
+        ctx.att, ctx.inc = att, inc
+        return spmm_csr(att.csr, Z, val=att.val, ex=ex())
 
     @staticmethod
     def backward(ctx, dY):
-        att, inc = ctx.att, ctx.inc
-        epi, slope, ln, eps, out_scale, s1, s2 = ctx.cfg
-        A, stats, gamma = ctx.saved_tensors
-        dY = dY.contiguous()
-        n, d = dY.shape
-        dev = dY.device
-        dgamma = dbeta = None
-        if not ln and epi == nat.EPI_NONE:
-            dZ = dY if out_scale == 1.0 else dY * out_scale  # a pure blend
-        else:
-            want_g = ln and ctx.needs_input_grad[1]
-            want_b = ln and ctx.needs_input_grad[2]
-            dgamma = torch.empty(d, dtype=torch.float32, device=dev) if want_g else None
-            dbeta = torch.empty(d, dtype=torch.float32, device=dev) if want_b else None
-            lib = nat.load()
-            wsb = (lib.hgd_row_epilogue_backward_workspace_size(n, d)
-                   if (want_g or want_b) else 0)
-            ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev) if wsb else None
-            dZ = torch.empty_like(dY)
-            nat.check(lib.hgd_row_epilogue_backward(
-                dY.data_ptr(), dY.stride(0), nat.ptr(A), 0 if A is None else A.stride(0),
-                nat.ptr(stats), nat.ptr(gamma), n, d, epi, float(slope), int(ln),
-                float(out_scale), dZ.data_ptr(), dZ.stride(0), nat.ptr(dgamma), nat.ptr(dbeta),
-                nat.ptr(ws), wsb, nat.stream_handle(dev)), "hgd_row_epilogue_backward")
+        att = ctx.att
+        need_dx = ctx.needs_input_grad[0]
+        dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
+            ctx, dY.contiguous(), need_dx)
         dX = None
-        if ctx.needs_input_grad[0]:
-            dX = spmm_csr(att.csr, _att_hops(att, inc, dZ), val=att.val)
-        return (dX, dgamma, dbeta, _res_grad(ctx, dY, 0, s1), _res_grad(ctx, dY, 1, s2), None,
-                None, None)
+        if need_dx:
+            if dz_scale != 1.0:  # a pure blend
+                dZ = dZ * dz_scale
+            dX = spmm_csr(att.csr, _att_hops(att, ctx.inc, dZ), val=att.val)
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None
 
 
 def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
@@ -423,33 +448,15 @@ def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
     fused store cannot hold (LayerNorm with d > 256, or a negative slope) run the same math as
     separate device ops."""
     _check_att(att, inc, X, "att_two_hop_fused")
-    epi = _EPI[epilogue]
     for t in (res1, res2):
         if t is not None and t.dtype != torch.float32:
             raise TypeError(f"att_two_hop_fused: float32 only, got {t.dtype}")
-    d = X.shape[1]
-    ln = norm is not None
-    if ln and (tuple(norm.normalized_shape) != (d,)):
-        raise ValueError(f"att_two_hop_fused: LayerNorm over {tuple(norm.normalized_shape)}, "
-                         f"d={d}")
-    for r in (res1, res2):
-        if r is not None and tuple(r.shape) != (att.n_rows, d):
-            raise ValueError(f"att_two_hop_fused: residual {tuple(r.shape)} != "
-                             f"{(att.n_rows, d)}")
-    if (ln and not _ln_supported(d)) or (epi != nat.EPI_NONE and slope < 0):
+    gamma, beta, cfg, fusable = _row_epilogue_cfg(
+        "att_two_hop_fused", att.n_rows, X.shape[1], epilogue, slope, norm, out_scale, res1,
+        res1_scale, res2, res2_scale)
+    if not fusable:
         y = att_two_hop(att, inc, X, epilogue=epilogue, slope=slope)
-        if ln:
-            y = norm(y)
-        y = out_scale * y
-        if res1 is not None:
-            y = y + res1_scale * res1
-        if res2 is not None:
-            y = y + res2_scale * res2
-        return y
-    gamma = norm.weight if ln and norm.weight is not None else None
-    beta = norm.bias if ln and norm.bias is not None else None
-    cfg = (epi, float(slope), ln, float(norm.eps) if ln else 0.0, float(out_scale),
-           float(res1_scale), float(res2_scale))
+        return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
     return _FusedAttTwoHop.apply(X, gamma, beta, res1, res2, att, inc, cfg)
 
 
@@ -760,63 +767,22 @@ class _RowEpilogue(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Z, gamma, beta, res1, res2, cfg):
-        epi, slope, ln, eps, out_scale, s1, s2 = cfg
         Z = Z.contiguous()
         n, d = Z.shape
-        dev = Z.device
-        need_a = ln or epi != nat.EPI_NONE
-        A = (Z if epi == nat.EPI_NONE else torch.empty_like(Z)) if need_a else None
-        stats = torch.empty((n, 2), dtype=torch.float32, device=dev) if ln else None
-        res1 = None if res1 is None else res1.contiguous()
-        res2 = None if res2 is None else res2.contiguous()
-        ex = nat.RowEpilogue(
-            act=epi, slope=slope, layer_norm=int(ln), ln_eps=eps,
-            ln_gamma=nat.ptr(gamma) if ln else None, ln_beta=nat.ptr(beta) if ln else None,
-            out_scale=out_scale,
-            res1=nat.ptr(res1), ld_res1=0 if res1 is None else res1.stride(0), res1_scale=s1,
-            res2=nat.ptr(res2), ld_res2=0 if res2 is None else res2.stride(0), res2_scale=s2,
-            act_out=nat.ptr(A) if (A is not None and A is not Z) else None,
-            ld_act=0 if A is None else A.stride(0), stats=nat.ptr(stats))
+        ex = _row_epilogue_setup(ctx, n, d, Z.device, gamma, beta, res1, res2, cfg, alias=Z)
         Y = torch.empty_like(Z)
-        nat.check(nat.load().hgd_row_epilogue_forward(
-            Z.data_ptr(), Z.stride(0), n, d, ctypes.byref(ex), Y.data_ptr(), Y.stride(0),
-            nat.stream_handle(dev)), "hgd_row_epilogue_forward")
-        ctx.cfg = cfg
-        ctx.has_res = (res1 is not None, res2 is not None)
-        ctx.save_for_backward(A, stats, gamma if ln else None)
+        _row_epilogue_forward(Z, ex(), Y)
         return Y
 
     @staticmethod
     def backward(ctx, dY):
-        epi, slope, ln, eps, out_scale, s1, s2 = ctx.cfg
-        A, stats, gamma = ctx.saved_tensors
-        dY = dY.contiguous()
-        n, d = dY.shape
-        dev = dY.device
-        lib = nat.load()
-        want_g = ln and ctx.needs_input_grad[1]
-        want_b = ln and ctx.needs_input_grad[2]
-        dgamma = torch.empty(d, dtype=torch.float32, device=dev) if want_g else None
-        dbeta = torch.empty(d, dtype=torch.float32, device=dev) if want_b else None
-        wsb = lib.hgd_row_epilogue_backward_workspace_size(n, d) if (want_g or want_b) else 0
-        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev) if wsb else None
-        dZ = None
-        if ctx.needs_input_grad[0] or want_g or want_b:
-            dZ = torch.empty_like(dY)
-            nat.check(lib.hgd_row_epilogue_backward(
-                dY.data_ptr(), dY.stride(0), nat.ptr(A), 0 if A is None else A.stride(0),
-                nat.ptr(stats), nat.ptr(gamma), n, d, epi, float(slope), int(ln),
-                float(out_scale), dZ.data_ptr(), dZ.stride(0), nat.ptr(dgamma), nat.ptr(dbeta),
-                nat.ptr(ws), wsb, nat.stream_handle(dev)),
-                "hgd_row_epilogue_backward")
-
-        def res_grad(k, s):
-            if not ctx.has_res[k] or not ctx.needs_input_grad[3 + k]:
-                return None
-            return dY if s == 1.0 else dY * s
-
-        return (dZ if ctx.needs_input_grad[0] else None, dgamma, dbeta, res_grad(0, s1),
-                res_grad(1, s2), None)
+        dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
+            ctx, dY.contiguous(), ctx.needs_input_grad[0])
+        if not ctx.needs_input_grad[0]:
+            dZ = None
+        elif dz_scale != 1.0:
+            dZ = dZ * dz_scale
+        return dZ, dgamma, dbeta, dres1, dres2, None
 
 
 def row_epilogue(Z: torch.Tensor, epilogue: Optional[str] = None, slope: float = 0.0,
@@ -824,17 +790,13 @@ def row_epilogue(Z: torch.Tensor, epilogue: Optional[str] = None, slope: float =
                  res1: Optional[torch.Tensor] = None, res1_scale: float = 1.0,
                  res2: Optional[torch.Tensor] = None, res2_scale: float = 1.0) -> torch.Tensor:
     """The fused store of :func:`two_hop_fused` applied to an existing [n, d] matrix."""
-    epi = _EPI[epilogue]
     d = Z.shape[-1]
-    ln = norm is not None
     if (Z.dim() != 2 or not Z.is_cuda or Z.dtype != torch.float32 or not _ln_supported(d)
-            or (epi != nat.EPI_NONE and slope < 0)):
+            or (_EPI[epilogue] != nat.EPI_NONE and slope < 0)):
         raise ValueError("row_epilogue: needs a 2-D float32 device matrix with d <= 256 "
                          "(d <= 64 when d % 4 != 0) and slope >= 0")
-    gamma = norm.weight if ln and norm.weight is not None else None
-    beta = norm.bias if ln and norm.bias is not None else None
-    cfg = (epi, float(slope), ln, float(norm.eps) if ln else 0.0, float(out_scale),
-           float(res1_scale), float(res2_scale))
+    gamma, beta, cfg, _ = _row_epilogue_cfg("row_epilogue", Z.shape[0], d, epilogue, slope, norm,
+                                            out_scale, res1, res1_scale, res2, res2_scale)
     return _RowEpilogue.apply(Z, gamma, beta, res1, res2, cfg)
 
 

@@ -685,6 +685,8 @@ def sharded_two_hop(sh: ShardedIncidence, X_local: torch.Tensor) -> torch.Tensor
 
 from . import _native as nat  # noqa: E402
 from .functional import _epilogue_apply, _epilogue_backward, _nn, _nt, _tn  # noqa: E402,F401
+from .functional import (_row_epilogue_backward, _row_epilogue_cfg,  # noqa: E402
+                         _row_epilogue_forward, _row_epilogue_setup, row_epilogue)
 
 
 class _AllReduceSum(torch.autograd.Function):
@@ -970,30 +972,12 @@ class _BipartiteHopFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, gamma, beta, res1, res2, sh: "ShardedBipartite", kind, cfg):
-        epi, slope, ln, eps, out_scale, s1, s2 = cfg
         X = X.contiguous()
         n = sh.n_local
         N, d = X.shape
         dev = X.device
         Y = torch.empty_like(X)
-        A = torch.empty_like(X) if (ln or epi != nat.EPI_NONE) else None
-        stats = torch.empty((N, 2), dtype=torch.float32, device=dev) if ln else None
-        res1 = None if res1 is None else res1.contiguous()
-        res2 = None if res2 is None else res2.contiguous()
-
-        def ex_rows(r0):  # the epilogue descriptor for local rows r0, r0+1, ...
-            return nat.RowEpilogue(
-                act=epi, slope=slope, layer_norm=int(ln), ln_eps=eps,
-                ln_gamma=nat.ptr(gamma) if ln else None, ln_beta=nat.ptr(beta) if ln else None,
-                out_scale=out_scale,
-                res1=None if res1 is None else res1[r0:].data_ptr(),
-                ld_res1=0 if res1 is None else res1.stride(0), res1_scale=s1,
-                res2=None if res2 is None else res2[r0:].data_ptr(),
-                ld_res2=0 if res2 is None else res2.stride(0), res2_scale=s2,
-                act_out=None if A is None else A[r0:].data_ptr(),
-                ld_act=0 if A is None else A.stride(0),
-                stats=None if stats is None else stats[r0:].data_ptr())
-
+        ex = _row_epilogue_setup(ctx, N, d, dev, gamma, beta, res1, res2, cfg)
         si, su = sh.scale("item", kind), sh.scale("user", kind)
         works: List = []
         Zi = None
@@ -1004,54 +988,25 @@ class _BipartiteHopFused(torch.autograd.Function):
                     spmm_csr(sh.C.csr, X[:n], val=sh.C.val, row_scale=si, out=Zi, row_begin=a,
                              row_end=b)
                 works.append(ordered_all_reduce(Zi[a:b], group=sh.group, async_op=True))
-        else:
-            spmm_csr(sh.C.csr, X[:n], val=sh.C.val, row_scale=si, out=Y[n:], ex=ex_rows(n))
-        spmm_csr(sh.B.csr, X[n:], val=sh.B.val, row_scale=su, out=Y[:n], ex=ex_rows(0))
+        else:  # the item rows are local rows n, n+1, ...
+            spmm_csr(sh.C.csr, X[:n], val=sh.C.val, row_scale=si, out=Y[n:], ex=ex(n))
+        spmm_csr(sh.B.csr, X[n:], val=sh.B.val, row_scale=su, out=Y[:n], ex=ex(0))
         for w in works:
             w.wait()
         if Zi is not None and sh.n_items:
-            ex = ex_rows(n)
-            nat.check(nat.load().hgd_row_epilogue_forward(
-                Zi.data_ptr(), Zi.stride(0), sh.n_items, d, ctypes.byref(ex), Y[n:].data_ptr(),
-                Y.stride(0), nat.stream_handle(dev)),
-                "hgd_row_epilogue_forward")
-        ctx.sh, ctx.kind, ctx.cfg = sh, kind, cfg
-        ctx.has_res = (res1 is not None, res2 is not None)
-        ctx.save_for_backward(A, stats, gamma if ln else None)
+            _row_epilogue_forward(Zi, ex(n), Y[n:])
+        ctx.sh, ctx.kind = sh, kind
         return Y
 
     @staticmethod
     def backward(ctx, dY):
-        epi, slope, ln, eps, out_scale, s1, s2 = ctx.cfg
-        A, stats, gamma = ctx.saved_tensors
-        dY = dY.contiguous()
-        N, d = dY.shape
-        dev = dY.device
-        want_g = ln and ctx.needs_input_grad[1]
-        want_b = ln and ctx.needs_input_grad[2]
-        dgamma = torch.empty(d, dtype=torch.float32, device=dev) if want_g else None
-        dbeta = torch.empty(d, dtype=torch.float32, device=dev) if want_b else None
-        if not ln and epi == nat.EPI_NONE:
-            dZ = dY if out_scale == 1.0 else dY * out_scale
-        else:
-            lib = nat.load()
-            wsb = lib.hgd_row_epilogue_backward_workspace_size(N, d) if (want_g or want_b) else 0
-            ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev) if wsb else None
-            dZ = torch.empty_like(dY)
-            nat.check(lib.hgd_row_epilogue_backward(
-                dY.data_ptr(), dY.stride(0), nat.ptr(A), 0 if A is None else A.stride(0),
-                nat.ptr(stats), nat.ptr(gamma), N, d, epi, float(slope), int(ln),
-                float(out_scale), dZ.data_ptr(), dZ.stride(0), nat.ptr(dgamma), nat.ptr(dbeta),
-                nat.ptr(ws), wsb, nat.stream_handle(dev)),
-                "hgd_row_epilogue_backward")
-        dX = _bipartite_backward(ctx.sh, ctx.kind, dZ) if ctx.needs_input_grad[0] else None
-
-        def res_grad(k, s):
-            if not ctx.has_res[k] or not ctx.needs_input_grad[3 + k]:
-                return None
-            return dY if s == 1.0 else dY * s
-
-        return dX, dgamma, dbeta, res_grad(0, s1), res_grad(1, s2), None, None, None
+        need_dx = ctx.needs_input_grad[0]
+        dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
+            ctx, dY.contiguous(), need_dx)
+        dX = None
+        if need_dx:
+            dX = _bipartite_backward(ctx.sh, ctx.kind, dZ if dz_scale == 1.0 else dZ * dz_scale)
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None
 
 
 def bipartite_hop_fused(sh: "ShardedBipartite", X_local: torch.Tensor,
@@ -1063,22 +1018,17 @@ def bipartite_hop_fused(sh: "ShardedBipartite", X_local: torch.Tensor,
     """``out_scale·norm(epi(S·A·X)) + res1_scale·res1 + res2_scale·res2`` on this rank's
     layout (functional.two_hop_fused's store for the sharded hop); falls back to the separate
     row pass where the fused store cannot hold a row (LayerNorm with d > 256)."""
-    from .functional import _EPI, _ln_supported, row_epilogue
     _require_f32(X_local, "bipartite_hop_fused")
     if X_local.shape[0] != sh.n_local + sh.n_items:
         raise ValueError(f"bipartite_hop_fused: X has {X_local.shape[0]} rows, shard expects "
                          f"{sh.n_local} users + {sh.n_items} items")
-    d = X_local.shape[1]
-    ln = norm is not None
-    epi = _EPI[epilogue]
-    if (ln and not _ln_supported(d)) or (epi != nat.EPI_NONE and slope < 0):
+    gamma, beta, cfg, fusable = _row_epilogue_cfg(
+        "bipartite_hop_fused", X_local.shape[0], X_local.shape[1], epilogue, slope, norm,
+        out_scale, res1, res1_scale, res2, res2_scale)
+    if not fusable:
         return row_epilogue(bipartite_hop(sh, X_local, scale), epilogue=epilogue, slope=slope,
                             norm=norm, out_scale=out_scale, res1=res1, res1_scale=res1_scale,
                             res2=res2, res2_scale=res2_scale)
-    gamma = norm.weight if ln and norm.weight is not None else None
-    beta = norm.bias if ln and norm.bias is not None else None
-    cfg = (epi, float(slope), ln, float(norm.eps) if ln else 0.0, float(out_scale),
-           float(res1_scale), float(res2_scale))
     return _BipartiteHopFused.apply(X_local, gamma, beta, res1, res2, sh, scale, cfg)
 
 

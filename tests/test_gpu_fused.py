@@ -66,6 +66,18 @@ def _check(o, act, slope, ln):
     X = o["X"]
     Z = O.two_hop(r, c, vals, shape, X, P, Q, R)
     magz = O.two_hop(r, c, None if vals is None else np.abs(vals), shape, np.abs(X), P, Q, R)
+
+    def back(dz, absolute=False):  # the two backward hops (of |A| for the magnitude)
+        v = vals if vals is None or not absolute else np.abs(vals)
+        return O.two_hop_backward(r, c, v, shape, None, dz, P, Q, R, None)
+
+    _check_rows(o, Z, magz, back, act, slope, ln)
+
+
+def _check_rows(o, Z, magz, back, act, slope, ln):
+    """The fused row epilogue over the linear operator whose float64 output is ``Z`` (``magz``
+    its Σ|terms|) and whose backward is ``back(dZ, absolute=False)``: Y, dX, the residual
+    gradients, dγ and dβ against the oracle, each bound scaled by the magnitude of its sum."""
     gamma = beta = None
     if ln:
         gamma = o["norm"].weight.detach().cpu().numpy().astype(np.float64)
@@ -85,7 +97,7 @@ def _check(o, act, slope, ln):
     assert_close(o["Y"], Yref, mag, what="fused fwd")
     # backward: dZ through the epilogue, then the two backward hops
     dZ, dg, db = O.row_epilogue_backward(Z, o["dY"], act, slope, ln, gamma, 1e-5, o["out_scale"])
-    dX = O.two_hop_backward(r, c, vals, shape, None, dZ, P, Q, R, None)
+    dX = back(dZ)
     dy = o["out_scale"] * np.abs(o["dY"])
     if ln:
         ah = np.abs(a - a.mean(-1, keepdims=True)) * rstd
@@ -96,8 +108,7 @@ def _check(o, act, slope, ln):
         mdz = dy
     if act == "leaky_relu":
         mdz = mdz * max(1.0, slope)
-    dmag = O.two_hop_backward(r, c, None if vals is None else np.abs(vals), shape, None, mdz,
-                              P, Q, R, None)
+    dmag = back(mdz, absolute=True)
     g = o["grads"]
     assert_close(g[0], dX, dmag, what="fused dX")
     for k, s in zip(range(len(res)), (o["s1"], o["s2"])):
@@ -269,3 +280,118 @@ def test_row_epilogue_standalone_vs_oracle(dev):
              + np.abs(xh) * np.abs(G * xh).mean(1, keepdims=True)) / sig
     terms *= np.where(Z > 0, 1.0, 0.2)
     assert np.all(np.abs(gZ.cpu().numpy() - dZ) <= 1e-5 * terms)
+
+
+# ---- every operator over the fused row epilogue: gradients of a subset of the inputs ---------
+_PARTIAL_CASES = [("leaky_relu", 0.2, True, 0.7), ("relu", 0.0, False, 0.7),
+                  (None, 0.0, False, 0.7), (None, 0.0, False, 1.0)]  # act, slope, LN, out_scale
+_SUBSETS = [("X",), ("gamma", "beta"), ("res1", "res2"), ("X", "res2")]
+
+
+def _long_row_coo(rng, n_rows, n_cols, nnz, row):
+    """~nnz random nonzeros, row ``row`` holding every column."""
+    r, c = random_coo(rng, n_rows, n_cols, nnz)
+    key = np.unique(np.concatenate([r * n_cols + c, row * n_cols + np.arange(n_cols)]))
+    return key // n_cols, key % n_cols
+
+
+def _partial_operator(op, dev, d, rng):
+    """``(n_rows, f)`` with ``f(X, res1, res2, **epilogue keywords) -> Y`` for one of the four
+    operators over the fused row epilogue."""
+    from hypergraph_diffusion_for_recommendation_amd import functional as F
+    if op == "bipartite_hop_fused":
+        from hypergraph_diffusion_for_recommendation_amd import sharded as S
+        r, c = _long_row_coo(rng, 37, 23, 300, 5)
+        sh = S.ShardedBipartite(_inc(r, c, rng.random(len(r)) + 0.1, (37, 23), dev))
+        return 60, lambda X, **kw: S.bipartite_hop_fused(sh, X, scale="mean", **kw)
+    if op == "row_epilogue":
+        return 70, lambda X, **kw: F.row_epilogue(X, **kw)
+    r, c = _long_row_coo(rng, 70, 45, 600, 7)
+    inc = _inc(r, c, rng.random(len(r)) + 0.1, (70, 45), dev)
+    if op == "two_hop_fused":
+        # Q = None at d = 20: the pure blend's backward then has no column scale to fold into
+        Q = None if d == 20 else "mean"
+        return 70, lambda X, **kw: F.two_hop_fused(inc, X, P="sym", Q=Q, R="sym", **kw)
+    ar, ac = random_coo(rng, 70, 70, 400)  # a row-stochastic attention (some rows empty)
+    w = rng.random(len(ar)) + 0.1
+    att = _inc(ar, ac, w / np.bincount(ar, weights=w, minlength=70)[ar], (70, 70), dev)
+    return 70, lambda X, **kw: F.att_two_hop_fused(att, inc, X, **kw)
+
+
+@pytest.mark.parametrize("d", [20, 64])
+@pytest.mark.parametrize("case", _PARTIAL_CASES, ids=["ln-leaky", "relu", "blend", "blend1"])
+@pytest.mark.parametrize("op", ["two_hop_fused", "att_two_hop_fused", "row_epilogue",
+                                "bipartite_hop_fused"])
+def test_partial_gradients(dev, op, case, d):
+    """The gradients of a subset of (X, γ, β, res1, res2) are bitwise those of the run in which
+    every input requires one, and Y does not depend on who asks: the backward skips what nobody
+    needs (the epilogue's kernel when neither dZ, dγ nor dβ is wanted) and nothing else."""
+    act, slope, ln, out_scale = case
+    rng = np.random.default_rng(1000 * d + 10 * _PARTIAL_CASES.index(case) + len(op))
+    n, f = _partial_operator(op, dev, d, rng)
+    t = {k: torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+         for k in ("X", "res1", "res2", "dY")}
+    norm = None
+    if ln:
+        norm = torch.nn.LayerNorm(d).to(dev)
+        with torch.no_grad():
+            norm.weight.copy_(torch.from_numpy(rng.random(d).astype(np.float32) + 0.5))
+            norm.bias.copy_(torch.from_numpy(rng.standard_normal(d).astype(np.float32)))
+
+    def run(names):
+        leaf = {k: t[k].clone().requires_grad_(k in names) for k in ("X", "res1", "res2")}
+        if ln:
+            leaf["gamma"] = norm.weight.requires_grad_("gamma" in names)
+            leaf["beta"] = norm.bias.requires_grad_("beta" in names)
+        Y = f(leaf["X"], res1=leaf["res1"], res2=leaf["res2"], epilogue=act, slope=slope,
+              norm=norm, out_scale=out_scale, res1_scale=1.0, res2_scale=0.3)
+        names = [k for k in names if k in leaf]
+        if not names:  # γ and β of a case without LayerNorm: nothing to differentiate
+            return Y.detach(), {}
+        return Y.detach(), dict(zip(names, torch.autograd.grad(Y, [leaf[k] for k in names],
+                                                                t["dY"])))
+
+    Y, full = run(("X", "gamma", "beta", "res1", "res2"))
+    for names in _SUBSETS:
+        Ys, part = run(names)
+        assert torch.equal(Ys, Y), (names, "Y")
+        for k, g in part.items():
+            assert torch.equal(g, full[k]), (names, k)
+
+
+@pytest.mark.parametrize("d", [20, 64])
+def test_bipartite_hop_fused_one_rank_vs_oracle(dev, d):
+    """bipartite_hop_fused on one rank, where the user rows and the item rows both take the
+    fused store (the item rows through a descriptor offset by the user rows): Y and the five
+    gradients against the float64 oracle over the bipartite matrix [[0, B], [Bᵀ, 0]]."""
+    from hypergraph_diffusion_for_recommendation_amd import sharded as S
+    rng = np.random.default_rng(d)
+    nu, ni = 37, 23
+    r, c = _long_row_coo(rng, nu, ni, 300, 5)
+    vals = (rng.random(len(r)) + 0.1).astype(np.float32)
+    sh = S.ShardedBipartite(_inc(r, c, vals, (nu, ni), dev))
+    N = nu + ni
+    ar, ac, av = np.concatenate([r, c + nu]), np.concatenate([c + nu, r]), np.tile(vals, 2)
+    p = np.lexsort((ac, ar))
+    rowptr, col, av = np.concatenate([[0], np.cumsum(np.bincount(ar, minlength=N))]), ac[p], av[p]
+    X = rng.standard_normal((N, d)).astype(np.float32)
+    res = [rng.standard_normal((N, d)).astype(np.float32) for _ in range(2)]
+    dY = rng.standard_normal((N, d)).astype(np.float32)
+    norm = torch.nn.LayerNorm(d).to(dev)
+    with torch.no_grad():
+        norm.weight.copy_(torch.from_numpy(rng.random(d).astype(np.float32) + 0.5))
+        norm.bias.copy_(torch.from_numpy(rng.standard_normal(d).astype(np.float32)))
+    Xt, r1, r2 = (torch.from_numpy(x).to(dev).requires_grad_(True) for x in (X, *res))
+    Y = S.bipartite_hop_fused(sh, Xt, epilogue="leaky_relu", slope=0.2, norm=norm, out_scale=0.7,
+                              res1=r1, res1_scale=1.0, res2=r2, res2_scale=0.3)
+    grads = torch.autograd.grad(Y, [Xt, r1, r2, norm.weight, norm.bias],
+                                torch.from_numpy(dY).to(dev))
+    o = dict(X=X, res=res, dY=dY, norm=norm, out_scale=0.7, s1=1.0, s2=0.3,
+             Y=Y.detach().cpu().numpy(), grads=[g.detach().cpu().numpy() for g in grads])
+    Z = O.spmm_csr(rowptr, col, X, val=av)
+    magz = O.spmm_csr(rowptr, col, X, val=av, absolute=True)
+
+    def back(dz, absolute=False):  # the matrix is symmetric: its backward is itself
+        return O.spmm_csr(rowptr, col, dz, val=av, absolute=absolute)
+
+    _check_rows(o, Z, magz, back, "leaky_relu", 0.2, True)
