@@ -10,6 +10,7 @@ with the reference's operator signatures:
 * :mod:`.layers`     — drop-in ``GCNLayer``, ``HGNNLayer``, ``HGCNConv``, ``SpAdjDropEdge``,
                        ``EquivSetConv``, ``EquivSetGNN``, ``MLP``
 * :mod:`.kg_attention` — KHGRec's per-batch KG attention (triple scores, row softmax) on device
+* :mod:`.kg_loss`    — KHGRec's TransR KG loss, fused forward and backward (no [B, d, dr] gather)
 * :mod:`.sharded`    — user-row sharding across GPUs with an RCCL all-reduce of hyperedge sums
 """
 from . import _native
@@ -17,8 +18,9 @@ from .incidence import CSR, Incidence, incidence_of, spmm_csr
 from .functional import (att_two_hop, att_two_hop_fused, contrast_loss, hgconv2, mean2hop, spmm,
                          two_hop, unique_long)
 from .kg_attention import KGAttentionPattern, kg_attention
+from .kg_loss import kg_loss, kg_loss_rows
 
 __all__ = ["CSR", "Incidence", "incidence_of", "spmm_csr", "spmm", "two_hop", "hgconv2",
            "mean2hop", "contrast_loss", "unique_long", "att_two_hop", "att_two_hop_fused",
-           "KGAttentionPattern", "kg_attention", "_native"]
+           "KGAttentionPattern", "kg_attention", "kg_loss", "kg_loss_rows", "_native"]
 __version__ = "0.1.0"

@@ -448,6 +448,14 @@ _SIGNATURES = {
     "hgd_kg_attention_softmax_workspace_size": (c_size, [c_i64]),
     "hgd_kg_attention_softmax": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
                                          c_void_p, c_void_p, c_size, c_void_p]),
+    "hgd_kg_loss_workspace_size": (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    "hgd_kg_loss_forward": (c_i32, [c_void_p, c_i64, c_void_p] * 3 + [
+        c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_i64, c_f32, c_i64,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "hgd_kg_loss_backward": (c_i32, [c_void_p, c_i64, c_void_p] * 3 + [
+        c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_i64, c_f32, c_i64,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size,
+        c_void_p]),
 }
 
 _lib = None

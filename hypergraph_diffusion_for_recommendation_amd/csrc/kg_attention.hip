@@ -7,6 +7,7 @@
 
 #include "device_util.h"
 #include "hgd_internal.h"
+#include "kg_tile.h"
 
 namespace hgd {
 namespace {
@@ -18,7 +19,7 @@ namespace {
 // Thread (slot, lane): relation-space column k = 32·kc + lane of the kTT triples of its slot;
 // the projections are fmaf chains over the embedding columns in ascending order, the sum over k
 // a per-lane chain over kc followed by a 32-lane xor butterfly.
-constexpr int kTile = 32;
+constexpr int kTile = kKgTile;
 constexpr int kKC = 32;
 constexpr int kJC = 128;
 constexpr int kSlots = kBlock / kKC;
@@ -41,39 +42,8 @@ __global__ __launch_bounds__(kBlock) void k_kg_scores(
   float* Et = smem + kTile * kJC;
   float* Ws = smem + 2 * kTile * kJC;
 
-  // which (relation, tile) this workgroup is: the tiles of the enabled relations are numbered in
-  // relation order; every wave finds the answer for itself with a 64-wide prefix scan
-  const int lane64 = threadIdx.x & 63;
-  int rem = static_cast<int>(blockIdx.x);
-  int rel = -1, base = 0, end = 0;
-  for (int c = 0; c < n_rel; c += 64) {
-    const int r = c + lane64;
-    int lo = 0, cnt = 0;
-    if (r < n_rel && (rel_enable == nullptr || rel_enable[r])) {
-      lo = static_cast<int>(rel_off[r]);
-      cnt = static_cast<int>(rel_off[r + 1]) - lo;
-    }
-    const int nt = (cnt + kTile - 1) / kTile;
-    int inc = nt;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-      const int o = __shfl_up(inc, m, 64);
-      if (lane64 >= m) inc += o;
-    }
-    const int total = __shfl(inc, 63, 64);
-    if (rem < total) {
-      const unsigned long long hit = __ballot(inc > rem);
-      const int L = __ffsll(static_cast<long long>(hit)) - 1;
-      const int before = __shfl(inc - nt, L, 64);
-      const int lo_l = __shfl(lo, L, 64);
-      const int cnt_l = __shfl(cnt, L, 64);
-      rel = c + L;
-      base = lo_l + (rem - before) * kTile;
-      end = lo_l + cnt_l;
-      break;
-    }
-    rem -= total;
-  }
+  // which (relation, tile) this workgroup is (kg_tile.h)
+  HGD_KG_FIND_TILE(n_rel, rel_off, rel_enable, rel, base, end);
   if (rel < 0) return;  // a surplus workgroup (the grid is the bound ⌈B/kTile⌉ + relations)
   const int n_here = min(kTile, end - base);
 

@@ -39,12 +39,12 @@ from .incidence import CSR, DEFAULT_SPLIT_CHUNK, Incidence, _gather32, _stream, 
 __all__ = ["KGAttentionPattern", "kg_attention", "relation_mask"]
 
 
-def _index_vector(x, name: str) -> torch.Tensor:
+def _index_vector(x, name: str, what: str = "KGAttentionPattern") -> torch.Tensor:
     if not isinstance(x, torch.Tensor) or x.dtype != torch.int64:
-        raise TypeError(f"KGAttentionPattern: {name} must be an int64 LongTensor, got "
+        raise TypeError(f"{what}: {name} must be an int64 LongTensor, got "
                         f"{getattr(x, 'dtype', type(x).__name__)}")
     if x.dim() != 1:
-        raise ValueError(f"KGAttentionPattern: {name} must be 1-D, got {tuple(x.shape)}")
+        raise ValueError(f"{what}: {name} must be 1-D, got {tuple(x.shape)}")
     return x
 
 

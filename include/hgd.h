@@ -28,6 +28,9 @@
  *   hgd_kg_attention_scores  update_attention_batch and its per-relation loop,
  *                            model/graph/KHGRec.py:298-320
  *   hgd_kg_attention_softmax torch.sparse.softmax(A_in.cpu(), dim=1), KHGRec.py:326-331
+ *   hgd_kg_loss_forward      calculate_kg_loss, KHGRec.py:347-365 (trans_M[r], three torch.bmm,
+ *                            logsigmoid, l2_reg_loss; also HD.py:371, HD2.py:368)
+ *   hgd_kg_loss_backward     its autograd backward (the [B, d, dr] gradient and its index_put)
  *
  * Conventions:
  *   - All pointers are DEVICE pointers unless a parameter says "host".
@@ -1235,6 +1238,73 @@ hgd_status hgd_kg_attention_softmax(const int64_t* rowptr, const int32_t* col,
                                     const int32_t* perm, int64_t n_rows, int64_t B,
                                     const float* v, float* val, void* workspace,
                                     size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * KG loss: KHGRec's calculate_kg_loss (model/graph/KHGRec.py:347-365, called on every minibatch,
+ * :144), the TransR loss of a batch of B triples (h, r, pos_t, neg_t), forward and backward,
+ * without the [B, d, dr] gather W_r = trans_M[r] and its gradient. fp32, every sum in a fixed
+ * order, no float atomics: two runs are bitwise equal. With W = W[r_i], e = R[r_i]:
+ *   a_i = x_h,i·W, p_i = x_p,i·W, n_i = x_n,i·W                                   (length dr)
+ *   pos_i = Σ_k (a + e − p)_k²,  neg_i = Σ_k (a + e − n)_k²
+ *   loss = (1/B) Σ_i softplus(pos_i − neg_i)
+ *          + reg_kg · (‖A‖_F + ‖E_r‖_F + ‖P‖_F + ‖N‖_F) / batch_size_kg
+ *   A, E_r, P, N the [B, dr] matrices of a_i, e (gathered: a relation counts once per triple),
+ *   p_i, n_i; the norms are not squared (util/loss_torch.py:17-21). −logsigmoid(neg − pos) is
+ *   evaluated as a stable softplus (finite for any finite difference). A norm that is exactly 0
+ *   contributes 0 and a 0 gradient. The mean divides by B, the regulariser by batch_size_kg
+ *   (they differ on a ragged last batch).
+ *
+ * Row sources: x_s (s = h, p, n) is a pointer, a leading dimension lds >= d and an int32 index
+ *   array is [B] or NULL: row i of kind s is x_s + (is ? is[i] : i)·lds. The table form passes
+ *   the same [n_ent, d] table three times with h, pos_t, neg_t; the drop-in form passes three
+ *   gathered [B, d] tensors without indices. Rows need no alignment (they are staged
+ *   element-wise). Indices are not range-checked here (hgd_index_narrow does that).
+ * W: [n_rel, d, dr] contiguous (trans_M); R: [n_rel, dr] rows ldR apart (relation_emb);
+ *   grp_perm / rel_off: the relation-grouped order of the batch, as for hgd_kg_attention_scores
+ *   (all relations take part). 1 <= n_rel <= 65535, d·dr <= 2^24, 0 < B < 2^31 / 3; B = 0 is
+ *   rejected (the mean over no triples is undefined).
+ *
+ * hgd_kg_loss_forward — a workgroup takes 32 consecutive triples of one relation in the grouped
+ *   order and reads W_r once (from LDS when d·dr·4 bytes fit beside the 24 KB of staged rows:
+ *   up to 36 KB; through the cache otherwise); the loss and the four sums of squares are reduced
+ *   per tile and then over the tiles in tile order by one workgroup. Written in full:
+ *   proj  fp32 [3, B, dr]: a, p, n in GROUPED order (row q of a plane is triple grp_perm[q]);
+ *   coef  fp32 [B]: σ(pos − neg)/B, grouped order;   norms fp32 [4]: ‖A‖, ‖E_r‖, ‖P‖, ‖N‖;
+ *   loss  fp32 [1].
+ *
+ * hgd_kg_loss_backward — `grad` is a device scalar (∂/∂loss, as in hgd_bpr_backward); proj, coef,
+ *   norms are the forward's. Each output is optional (NULL = not computed):
+ *   G   fp32 [3B, d] contiguous, written in full: row s·B + i = grad · ∂loss/∂x_s,i = W_r·g_s,i
+ *       in the BATCH's order (s = 0, 1, 2 for h, pos_t, neg_t). For the table form the entity
+ *       gradient is S·G with the binary [n_ent, 3B] matrix "entity ← position" (hgd_sort_perm
+ *       over the 3B ids, hgd_rowptr_from_sorted, hgd_spmm): pull-style, untouched rows 0.
+ *   dW  fp32 [n_rel, d, dr] and dR fp32 [n_rel, dr], both or neither, written in full: for
+ *       relation r the sum over r's triples of x_h ⊗ g_a + x_p ⊗ g_p + x_n ⊗ g_n and of g_e,
+ *       taken per 32-triple tile in grouped order and then over r's tiles in tile order (one
+ *       output element per thread); a relation without triples gets exact zeros. Duplicates of
+ *       a triple are counted once each, as the reference's gather does.
+ *
+ * Workspace: hgd_kg_loss_workspace_size(B, n_rel, d, dr) for either call (the tiles' partial
+ * sums; ⌈B/32⌉ + min(n_rel, B) tiles of (d + 1)·dr floats for dW / dR). Stream-ordered, no host
+ * synchronisation, no allocation. */
+size_t hgd_kg_loss_workspace_size(int64_t B, int32_t n_rel, int32_t d, int32_t dr);
+hgd_status hgd_kg_loss_forward(const float* xh, int64_t ldh, const int32_t* ih, const float* xp,
+                               int64_t ldp, const int32_t* ip, const float* xn, int64_t ldn,
+                               const int32_t* in, const float* W, const float* R, int64_t ldR,
+                               int32_t n_rel, int32_t d, int32_t dr, const int32_t* grp_perm,
+                               const int64_t* rel_off, int64_t B, float reg_kg,
+                               int64_t batch_size_kg, float* proj, float* coef, float* norms,
+                               float* loss, void* workspace, size_t workspace_bytes,
+                               void* stream);
+hgd_status hgd_kg_loss_backward(const float* xh, int64_t ldh, const int32_t* ih, const float* xp,
+                                int64_t ldp, const int32_t* ip, const float* xn, int64_t ldn,
+                                const int32_t* in, const float* W, const float* R, int64_t ldR,
+                                int32_t n_rel, int32_t d, int32_t dr, const int32_t* grp_perm,
+                                const int64_t* rel_off, int64_t B, float reg_kg,
+                                int64_t batch_size_kg, const float* proj, const float* coef,
+                                const float* norms, const float* grad, float* G, float* dW,
+                                float* dR, void* workspace, size_t workspace_bytes,
+                                void* stream);
 
 #ifdef __cplusplus
 }

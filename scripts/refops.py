@@ -86,6 +86,23 @@ def att_hgcn_conv(inp_adj, att_adj, embs, act=True, slope=0.5):
     return F.leaky_relu(Y, slope) if act else Y
 
 
+def kg_loss_ref(h_embed, r, pos_t_embed, neg_t_embed, trans_M, relation_emb, reg_kg,
+                batch_size_kg):
+    """What KHGRec's calculate_kg_loss computes per minibatch (KHGRec.py:347-365), with the same
+    torch ops in the same places: the [B, d, dr] gather trans_M[r] and the [B, dr] gather of
+    relation_emb, three torch.bmm against the gathered matrices, the two squared distances,
+    −logsigmoid(neg − pos), its mean over the batch, and the four unsquared torch.norm of
+    l2_reg_loss (util/loss_torch.py:17-21) times reg_kg over the configured batch size."""
+    e = relation_emb[r]
+    W_r = trans_M[r]
+    a, p, n = (torch.bmm(x.unsqueeze(1), W_r).squeeze(1) for x in (h_embed, pos_t_embed,
+                                                                   neg_t_embed))
+    pos = torch.sum(torch.pow(a + e - p, 2), dim=1)
+    neg = torch.sum(torch.pow(a + e - n, 2), dim=1)
+    loss = torch.mean(-F.logsigmoid(neg - pos))
+    return loss + sum(torch.norm(x, p=2) for x in (a, e, p, n)) * reg_kg / batch_size_kg
+
+
 def contrast_loss(embeds1, embeds2, nodes, temp):
     """contrastLoss (util/loss_torch.py:103-110)."""
     embeds1 = F.normalize(embeds1 + 1e-8, p=2)
