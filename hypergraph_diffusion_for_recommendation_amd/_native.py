@@ -257,6 +257,14 @@ _SIGNATURES = {
                                  c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32, c_f32,
                                  ctypes.POINTER(SplitPlan), c_void_p, c_size, c_void_p,
                                  c_void_p]),
+    "hgd_spmm_block_order_for": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_i32]),
+    "hgd_spmm_col_blocks_ordered_workspace_size": (c_size, [c_i64, c_i32]),
+    "hgd_spmm_col_blocks_ordered": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size,
+                                            c_void_p]),
+    "hgd_spmm_blocked_ordered": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                         c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32,
+                                         c_f32, c_i32, c_void_p]),
     "hgd_spmm_masked": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_void_p, c_i64,
                                 c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32,
                                 c_i32, c_f32, ctypes.POINTER(SplitPlan), c_void_p, c_size,

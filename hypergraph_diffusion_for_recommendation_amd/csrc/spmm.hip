@@ -162,6 +162,44 @@ RowOrderWs row_order_ws(int64_t n_rows) {
   return w;
 }
 
+// Block order (hgd_spmm_col_blocks_ordered): dest[k·n_rows + out_row[k·n_rows + p]] =
+// blk_start[k·n_rows + p], where row r's piece of block k starts in the ordered copy — the start
+// array col_block_scatter_kernel moves the nonzeros by. n = n_blk·n_rows.
+__global__ void block_order_dest_kernel(const int64_t* __restrict__ blk_start,
+                                        const int32_t* __restrict__ out_row, int64_t n_rows,
+                                        int64_t n, int64_t* __restrict__ dest) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  dest[i - i % n_rows + out_row[i]] = blk_start[i];
+}
+
+// workspace of hgd_spmm_col_blocks_ordered: the block-major counts (then the permuted lengths),
+// the natural block-major starts (then the scatter's destinations), one block's keys and sorted
+// keys, then the sort's and the scan's own (one after the other in the same tail)
+struct BlockOrderWs {
+  size_t cnt, start, keys, keys_s, tail, total;
+};
+
+BlockOrderWs block_order_ws(int64_t n_rows, int32_t n_blk) {
+  BlockOrderWs w{};
+  const int64_t n = static_cast<int64_t>(n_blk) * n_rows + 1;
+  size_t scan = 0;
+  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan, static_cast<const int64_t*>(nullptr),
+                                       static_cast<int64_t*>(nullptr), n) != hipSuccess)
+    return w;
+  const size_t sort = hgd_sort_perm_workspace_size(n_rows);
+  if (sort == 0) return w;
+  const size_t a = align_up(static_cast<size_t>(n) * sizeof(int64_t));
+  const size_t k = align_up(static_cast<size_t>(n_rows) * sizeof(int32_t));
+  w.cnt = 0;
+  w.start = a;
+  w.keys = 2 * a;
+  w.keys_s = w.keys + k;
+  w.tail = w.keys_s + k;
+  w.total = w.tail + (sort > align_up(scan) ? sort : align_up(scan));
+  return w;
+}
+
 }  // namespace
 }  // namespace hgd
 
@@ -223,6 +261,22 @@ extern "C" int32_t hgd_spmm_row_order_for(int64_t n_rows, int64_t n_src_rows, in
   if (nnz > 32 * n_rows) return 0;
   // between the two bounds it is on: at 10 M users × 1 M items × 100 M edges the ordered hop into
   // users is 7–8 % faster at d = 32, 64 and 128 (scripts/bench_row_order.py)
+  return 1;
+}
+
+extern "C" int32_t hgd_spmm_block_order_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz,
+                                            int32_t d, int32_t n_blocks) {
+  if (n_rows <= 0 || n_src_rows <= 0 || nnz <= 0 || d <= 0 || n_blocks <= 0) return 0;
+  // hgd_spmm_row_order_for's two bounds applied to one source block: the slice one pass gathers
+  // from (a blocked hop runs rows wider than 128 as 128-column passes) fits the aggregate L2 ...
+  const double slice =
+      static_cast<double>(n_src_rows) / n_blocks * (d < 128 ? d : 128) * 4.0;
+  if (slice < 33554432.0) return 0;
+  // ... or the order turns one gather of a long piece
+  if (nnz > 32 * static_cast<int64_t>(n_blocks) * n_rows) return 0;
+  // between the two bounds it is on: at 10 M users × 1 M items × 100 M edges the hop into items
+  // is 1.4 % faster at d = 64 (P = 4) and 3.9 % at d = 128 (P = 8), with 2.4 % less fetched at
+  // d = 64 (scripts/bench_mall_blocked.py --block-order both)
   return 1;
 }
 
@@ -323,6 +377,98 @@ extern "C" hgd_status hgd_spmm_blocked(const int64_t* blk_start, const int32_t* 
   r.blocked = true;
   r.blk_start = blk_start;
   r.n_blk = n_blocks;
+  r.stream = stream;
+  return hgd::spmm_launch<float, float>(r);
+}
+
+extern "C" size_t hgd_spmm_col_blocks_ordered_workspace_size(int64_t n_rows, int32_t n_blocks) {
+  if (n_rows <= 0 || n_rows >= 0x7fffffffLL || n_blocks <= 0 || n_blocks > 64) return 0;
+  return hgd::block_order_ws(n_rows, n_blocks).total;
+}
+
+extern "C" hgd_status hgd_spmm_col_blocks_ordered(const int64_t* rowptr, const int32_t* col,
+                                                  int64_t n_rows, int64_t n_cols,
+                                                  int32_t n_blocks, int64_t* blk_start,
+                                                  int32_t* blk_col, int32_t* blk_perm,
+                                                  int32_t* blk_out_row, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
+  using namespace hgd;
+  clear_error();
+  constexpr const char* fn = "hgd_spmm_col_blocks_ordered";
+  HGD_REQUIRE(n_rows >= 0 && n_cols >= 0, "%s: negative sizes", fn);
+  HGD_REQUIRE(n_blocks >= 1 && n_blocks <= 64, "%s: blocks must be 1..64", fn);
+  HGD_REQUIRE(n_rows < 0x7fffffffLL, "%s: n_rows >= 2^31 - 1", fn);
+  HGD_REQUIRE(n_cols < 0x7fffffffLL, "%s: n_cols >= 2^31 - 1", fn);
+  if (n_rows == 0) return HGD_OK;
+  HGD_REQUIRE(rowptr && blk_start && blk_out_row, "%s: null rowptr / blk_start / blk_out_row", fn);
+  const BlockOrderWs w = block_order_ws(n_rows, n_blocks);
+  if (w.total == 0 || !workspace || workspace_bytes < w.total)
+    return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < %zu", fn, workspace_bytes, w.total);
+  const int64_t n = static_cast<int64_t>(n_blocks) * n_rows;
+  const int64_t row_grid = (n_rows + 255) / 256;
+  constexpr int kRowsPerBlock = kBlock / kOrdG;
+  const int64_t key_grid = (n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  hipStream_t st = as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  int64_t* cnt = reinterpret_cast<int64_t*>(ws + w.cnt);      // then the permuted lengths
+  int64_t* start = reinterpret_cast<int64_t*>(ws + w.start);  // then the scatter's destinations
+  int32_t* keys = reinterpret_cast<int32_t*>(ws + w.keys);
+  int32_t* keys_s = reinterpret_cast<int32_t*>(ws + w.keys_s);
+  size_t tail_bytes = workspace_bytes - w.tail;
+  // the natural block-major copy (hgd_spmm_col_blocks' three steps), into blk_col itself: the
+  // keys below are read from it, and the second scatter overwrites it
+  hipLaunchKernelGGL(col_block_count_kernel, dim3(row_grid), dim3(256), 0, st, rowptr, col, n_rows,
+                     n_cols, n_blocks, cnt);
+  hgd_status s = check_launch(fn, "count");
+  if (s != HGD_OK) return s;
+  HGD_HIP(hipcub::DeviceScan::ExclusiveSum(ws + w.tail, tail_bytes, cnt, start, n + 1, st));
+  hipLaunchKernelGGL(col_block_scatter_kernel, dim3(row_grid), dim3(256), 0, st, rowptr, col,
+                     n_rows, n_cols, n_blocks, start, blk_col, static_cast<int32_t*>(nullptr));
+  s = check_launch(fn, "scatter");
+  if (s != HGD_OK) return s;
+  // hgd_spmm_row_order's pattern over each block's own CSR (start + k·n_rows, blk_col): keys,
+  // stable sort (an empty piece has the key n_cols and sorts last), permuted lengths
+  for (int32_t k = 0; k < n_blocks; ++k) {
+    const int64_t off = static_cast<int64_t>(k) * n_rows;
+    hipLaunchKernelGGL(row_min_key_kernel, dim3(key_grid), dim3(kBlock), 0, st, start + off,
+                       blk_col, n_rows, static_cast<int32_t>(n_cols), keys);
+    s = check_launch(fn, "keys");
+    if (s != HGD_OK) return s;
+    s = hgd_sort_perm(keys, n_rows, n_cols + 1, keys_s, blk_out_row + off, ws + w.tail, tail_bytes,
+                      stream);
+    if (s != HGD_OK) return s;
+    // (writes the closing 0 at cnt[off + n_rows], which the next block's launch overwrites)
+    hipLaunchKernelGGL(row_order_len_kernel, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, st,
+                       start + off, blk_out_row + off, n_rows, cnt + off);
+    s = check_launch(fn, "lengths");
+    if (s != HGD_OK) return s;
+  }
+  HGD_HIP(hipcub::DeviceScan::ExclusiveSum(ws + w.tail, tail_bytes, cnt, blk_start, n + 1, st));
+  // every piece's start in the ordered copy, indexed by (block, row), and the nonzeros moved
+  // there from the source structure: blk_perm is their source position as in hgd_spmm_col_blocks
+  hipLaunchKernelGGL(block_order_dest_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, blk_start,
+                     blk_out_row, n_rows, n, start);
+  s = check_launch(fn, "destinations");
+  if (s != HGD_OK) return s;
+  hipLaunchKernelGGL(col_block_scatter_kernel, dim3(row_grid), dim3(256), 0, st, rowptr, col,
+                     n_rows, n_cols, n_blocks, start, blk_col, blk_perm);
+  return check_launch(fn, "ordered scatter");
+}
+
+extern "C" hgd_status hgd_spmm_blocked_ordered(const int64_t* blk_start, const int32_t* blk_col,
+                                               const float* blk_val, const float* blk_row_scale,
+                                               const int32_t* blk_out_row, int64_t n_rows,
+                                               int64_t n_src_rows, const float* X, int64_t ldx,
+                                               float* Y, int64_t ldy, int32_t d, int32_t epilogue,
+                                               float slope, int32_t n_blocks, void* stream) {
+  hgd::clear_error();
+  hgd::SpmmRequest r{"hgd_spmm_blocked_ordered", nullptr, blk_col, blk_val, blk_row_scale, n_rows,
+                     n_src_rows, 0, n_rows, X, ldx, Y, ldy, d, epilogue, slope};
+  r.blocked = true;
+  r.blk_start = blk_start;
+  r.n_blk = n_blocks;
+  r.ordered = true;
+  r.out_row = blk_out_row;
   r.stream = stream;
   return hgd::spmm_launch<float, float>(r);
 }

@@ -54,7 +54,9 @@ struct SpmmRequest {
   bool blocked = false;
   const int64_t* blk_start = nullptr;
   int32_t n_blk = 0;
-  // the row order (hgd_spmm_ordered): position p is written to Y row out_row[p]
+  // the row order (hgd_spmm_ordered): position p is written to Y row out_row[p]. With blocked
+  // (hgd_spmm_blocked_ordered) every source block has its own: out_row and row_scale are
+  // [n_blk·n_rows], block k's at k·n_rows, in the processing order of its blk_start
   bool ordered = false;
   const int32_t* out_row = nullptr;
 };
@@ -186,7 +188,8 @@ inline hgd_status spmm_check_args(const SpmmRequest& r) {
   const int32_t d = r.d;
   const hgd_row_epilogue* ex = r.ex;
   const bool empty = r.row_end == r.row_begin;
-  HGD_REQUIRE(!r.ordered || r.out_row || r.n_rows <= 0, "%s: null out_row", fn);
+  HGD_REQUIRE(!r.ordered || r.out_row || r.n_rows <= 0, "%s: null %s", fn,
+              r.blocked ? "blk_out_row" : "out_row");
   HGD_REQUIRE(!r.blocked || (r.n_blk >= 1 && r.n_blk <= 64), "%s: blocks must be 1..64", fn);
   HGD_REQUIRE(!r.blocked || r.blk_start || r.row_end <= r.row_begin, "%s: null blk_start", fn);
   HGD_REQUIRE(r.keep > 0.f, "%s: keep must be > 0 (got %g)", fn, (double)r.keep);  // (unmasked: 1)
@@ -220,12 +223,18 @@ inline hgd_status spmm_check_args(const SpmmRequest& r) {
   if (r.out_row) {
     // the ordered hop is the row kernel over every row: a split plan's chunks and fix-up and the
     // segmented walk index Y by position, a row range is one of positions, and the fused
-    // epilogue's side tables and the blocked hop's passes are indexed by row
+    // epilogue's side tables and the blocked hop's passes are indexed by row — unless the blocks
+    // bring their own orders (hgd_spmm_blocked_ordered: blocked and ordered together)
     if (has_split_rows(r.plan) || (r.plan && (r.plan->flags & HGD_PLAN_SEGMENTED)))
       return fail(HGD_ERR_UNSUPPORTED, "%s: no split rows or segmented walk with a row order", fn);
-    if (r.mask || ex || r.blocked)
+    if (r.blocked && r.ordered) {
+      if (r.mask || ex)
+        return fail(HGD_ERR_UNSUPPORTED, "%s: no mask or fused row epilogue with a block order",
+                    fn);
+    } else if (r.mask || ex || r.blocked) {
       return fail(HGD_ERR_UNSUPPORTED,
                   "%s: no mask, fused row epilogue or source blocks with a row order", fn);
+    }
     if (r.row_begin != 0 || r.row_end != r.n_rows)
       return fail(HGD_ERR_UNSUPPORTED, "%s: a row order covers all rows, got [%lld,%lld) of %lld",
                   fn, (long long)r.row_begin, (long long)r.row_end, (long long)r.n_rows);
@@ -379,7 +388,10 @@ hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmRequest& r, const SpmmPass
       hgd_status s;
       if (r.blocked) {
         a.rowptr = r.blk_start + static_cast<int64_t>(k) * r.n_rows;  // block k's own CSR
-        if constexpr (kF32<TX, TY>) {
+        if (r.ordered) {  // ... in its own row order (the row kernel only: no segmented walk)
+          a.out_row = r.out_row + static_cast<int64_t>(k) * r.n_rows;
+          if (r.row_scale) a.row_scale = r.row_scale + static_cast<int64_t>(k) * r.n_rows;
+        } else if constexpr (kF32<TX, TY>) {
           if (VEC == 4) a.seg = spmm_tuning().blocked_seg;  // (the vector path's only)
         }
         a.blk_accum = k > 0;

@@ -88,6 +88,8 @@ class CSR:
         self.cols_ascending = False
         self._col_blocks: Dict[int, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
         self._blk_vals: Dict[Tuple[int, int], tuple] = {}
+        self._col_blocks_ord: Dict[int, Tuple[torch.Tensor, ...]] = {}
+        self._blk_ord_vals: Dict[Tuple[int, int], tuple] = {}
         self._row_order: Optional[Tuple[torch.Tensor, ...]] = None
         self._ord_vals: Dict[Tuple[int, int], tuple] = {}
         self._plan_arrays = ()
@@ -190,6 +192,55 @@ class CSR:
         if val is None:
             return None
         return _gather32_cached(self._blk_vals, n_blocks, val, self.col_blocks(n_blocks)[2])
+
+    def col_blocks_ordered(self, n_blocks: int) -> Tuple[torch.Tensor, ...]:
+        """:meth:`col_blocks` with the rows of every source block in ascending order of their
+        first column in that block, for hgd_spmm_blocked_ordered (hgd_spmm_col_blocks_ordered):
+        ``(blk_start [n_blocks·n_rows+1] int64, blk_col [nnz] int32, blk_perm [nnz] int32,
+        blk_out_row [n_blocks·n_rows] int32)`` — position p of block k holds row
+        ``blk_out_row[k·n_rows + p]``. Built once per block count on the current stream."""
+        got = self._col_blocks_ord.get(n_blocks)
+        if got is None:
+            if not self.cols_ascending:
+                raise RuntimeError(
+                    "col_blocks_ordered: the rows' columns are not known to be ascending")
+            dev = self.device
+            lib = nat.load()
+            start = torch.empty(n_blocks * self.n_rows + 1, dtype=torch.int64, device=dev)
+            bcol = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+            perm = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+            out_row = torch.empty(n_blocks * self.n_rows, dtype=torch.int32, device=dev)
+            if self.n_rows:
+                ws = _ws(lib.hgd_spmm_col_blocks_ordered_workspace_size(self.n_rows, n_blocks),
+                         dev)
+                nat.check(lib.hgd_spmm_col_blocks_ordered(
+                    self.rowptr.data_ptr(), self.col.data_ptr() if self.nnz else None,
+                    self.n_rows, self.n_cols, n_blocks, start.data_ptr(),
+                    bcol.data_ptr() if self.nnz else None, perm.data_ptr() if self.nnz else None,
+                    out_row.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+                    "hgd_spmm_col_blocks_ordered")
+            else:
+                start.zero_()
+            got = self._col_blocks_ord[n_blocks] = (start, bcol, perm, out_row)
+        return got
+
+    def blocked_ordered_values(self, n_blocks: int,
+                               val: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """``val`` (per-nonzero weights) in the entry order of :meth:`col_blocks_ordered`; cached
+        like :meth:`blocked_values`."""
+        if val is None:
+            return None
+        return _gather32_cached(self._blk_ord_vals, 2 * n_blocks, val,
+                                self.col_blocks_ordered(n_blocks)[2])
+
+    def blocked_ordered_scale(self, n_blocks: int,
+                              row_scale: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """``row_scale`` (one per row) as ``[n_blocks·n_rows]`` in the processing order of
+        :meth:`col_blocks_ordered`; cached like :meth:`blocked_values`."""
+        if row_scale is None:
+            return None
+        return _gather32_cached(self._blk_ord_vals, 2 * n_blocks + 1, row_scale,
+                                self.col_blocks_ordered(n_blocks)[3])
 
     def row_order(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """The rows in ascending order of their smallest column, for the ordered hop
@@ -308,6 +359,31 @@ def spmm_row_order(csr: CSR, d: int) -> bool:
     return bool(nat.load().hgd_spmm_row_order_for(csr.n_rows, csr.n_cols, csr.nnz, int(d)))
 
 
+def spmm_block_order(csr: CSR, d: int, blocks: int) -> bool:
+    """Whether the fp32 source-blocked hop over ``csr`` at width ``d`` in ``blocks`` blocks
+    walks each block's rows in ascending order of their first column in that block
+    (hgd_spmm_blocked_ordered over :meth:`CSR.col_blocks_ordered`).
+
+    :func:`spmm_row_order`'s idea inside one source block: a row piece of ~25 nonzeros gathers
+    from the whole slice of the block, so pieces that share their first column processed next to
+    each other make that gather an L2 hit. Each piece's sum and the order of the blocks are
+    unchanged: Y is bitwise hgd_spmm_blocked's. The price is one 4-byte row id per row and
+    block, and the row scale gathered per block. The size rule is the library's
+    (hgd_spmm_block_order_for).
+
+    ``HGD_SPMM_BLOCK_ORDER``: ``0`` off, ``1`` on wherever the hop runs blocked, unset (or
+    ``auto``) = the size rule."""
+    if blocks <= 1 or csr.nnz == 0:
+        return False
+    env = os.environ.get("HGD_SPMM_BLOCK_ORDER", "")
+    if env not in ("", "auto"):
+        if env not in ("0", "1"):
+            raise ValueError(f"HGD_SPMM_BLOCK_ORDER must be 0 or 1, got {env!r}")
+        return env == "1"
+    return bool(nat.load().hgd_spmm_block_order_for(csr.n_rows, csr.n_cols, csr.nnz, int(d),
+                                                    int(blocks)))
+
+
 # element types of the hop's table and output -> HGD_DT_* (hgd_spmm_dt)
 _HOP_DTYPES = {torch.float32: nat.DT_F32, torch.bfloat16: nat.DT_BF16}
 
@@ -388,6 +464,9 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     # the plain fp32 hop over the whole row range may walk its rows in min-column order
     ordered = (not dt and mask is None and ex is None and not blocks and rb == 0 and re_ == n
                and spmm_row_order(csr, d))
+    # and the fp32 source-blocked hop over the whole row range each block's rows in its own
+    blk_ordered = (not dt and bool(blocks) and rb == 0 and re_ == n
+                   and spmm_block_order(csr, d, blocks))
     if ordered:
         order, rowptr_o, col_o, _ = csr.row_order()
         nat.check(lib.hgd_spmm_ordered(
@@ -423,6 +502,12 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
         nat.check(lib.hgd_spmm_masked(
             rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, ldx, yp, ldy, d, int(epilogue),
             float(slope), plan_ptr, wp, wsb, st), "hgd_spmm_masked")
+    elif blk_ordered:  # (blocks: no mask, no fused epilogue)
+        start, bcol, _, out_row = csr.col_blocks_ordered(blocks)
+        nat.check(lib.hgd_spmm_blocked_ordered(
+            start.data_ptr(), bcol.data_ptr(), nat.ptr(csr.blocked_ordered_values(blocks, val)),
+            nat.ptr(csr.blocked_ordered_scale(blocks, row_scale)), out_row.data_ptr(), n, m, xp,
+            ldx, yp, ldy, d, int(epilogue), float(slope), blocks, st), "hgd_spmm_blocked_ordered")
     elif ex is None and blocks:
         start, bcol, _ = csr.col_blocks(blocks)
         bval = csr.blocked_values(blocks, val)
@@ -442,11 +527,12 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
 
         def nbytes(csr=csr, rb=rb, re_=re_, full=full, d=d, hv=val is not None,
                    hs=row_scale is not None, blocks=blocks, xb=X.element_size(),
-                   yb=out.element_size(), ordered=ordered):
+                   yb=out.element_size(), ordered=ordered, blk_ordered=blk_ordered):
             nnz = csr.nnz if full else int(csr.rowptr[re_].item() - csr.rowptr[rb].item())
             return (profiling.hop_bytes(nnz, re_ - rb, d, x_bytes=xb, y_bytes=yb),
                     profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, blocks, x_bytes=xb,
-                                         y_bytes=yb, ordered=ordered))
+                                         y_bytes=yb, ordered=ordered,
+                                         block_ordered=blk_ordered))
 
         timer.end(t0, nbytes)
     return out
@@ -887,8 +973,10 @@ def expand_rows(rowptr: torch.Tensor, nnz: int) -> torch.Tensor:
 
 
 def _gather32(src: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
-    out = torch.empty_like(src)
+    """``src[perm]`` over 4-byte elements: as long as ``perm``, which need not be ``src``'s
+    length (a row scale gathered once per source block is n_blocks times as long)."""
     n = perm.numel()
+    out = torch.empty(n, dtype=src.dtype, device=src.device)
     if n:
         nat.check(nat.load().hgd_gather32(src.data_ptr(), perm.data_ptr(), n, out.data_ptr(),
                                           _stream(src.device)), "hgd_gather32")

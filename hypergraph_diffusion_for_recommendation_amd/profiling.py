@@ -36,16 +36,21 @@ def hop_bytes(nnz: int, rows: int, d: int, weighted: bool = False, x_bytes: int 
 
 
 def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
-               blocks: int = 0, x_bytes: int = 4, y_bytes: int = 4, ordered: bool = False) -> int:
+               blocks: int = 0, x_bytes: int = 4, y_bytes: int = 4, ordered: bool = False,
+               block_ordered: bool = False) -> int:
     """Bytes the hgd_spmm launch streams at minimum as implemented (int64 rowptr, weights).
     A source-blocked hop (hgd_spmm_blocked, ``blocks`` = P > 1) reads the [R × (P+1)] int64
     block starts instead of the rowptr, writes every Y row P times, reads it back P−1 times and
     applies the row scale in every pass. A blocked hop into a 16-bit Y (hgd_spmm_blocked_dt)
     keeps the running partial in an fp32 scratch instead: P−1 writes and P−1 reads of 4-byte
     rows, then one store of the 2-byte Y row. An ordered hop (hgd_spmm_ordered) also reads the
-    int32 output row of every row."""
+    int32 output row of every row, a blocked hop over per-block row orders
+    (hgd_spmm_blocked_ordered, ``block_ordered``) the one of every row in every block."""
     if ordered:
         return impl_bytes(nnz, rows, d, has_val, has_scale, 0, x_bytes, y_bytes) + rows * 4
+    if blocks > 1 and block_ordered:
+        return (impl_bytes(nnz, rows, d, has_val, has_scale, blocks, x_bytes, y_bytes)
+                + rows * blocks * 4)
     if blocks > 1:
         if y_bytes == 4:
             y_traffic = 4 * d * (2 * blocks - 1)

@@ -17,6 +17,8 @@
  *                            than the Infinity Cache (source-blocked; hgd_spmm_col_blocks builds
  *                            its block-major copy of the CSC)
  *   hgd_spmm_blocked_dt      the source-blocked hop over bfloat16 tables
+ *   hgd_spmm_blocked_ordered the source-blocked hop with each block's rows walked in ascending
+ *                            order of their first column (hgd_spmm_col_blocks_ordered builds it)
  *   hgd_sort_perm            COO→CSR / CSR→CSC ordering that cuSPARSE re-derives per call
  *                            (`adj.t()` in HGCNConv.forward, HGNN_HD4.py:459; coalesce in torch.sparse.mm)
  *   hgd_rowptr_from_sorted   row pointer of a row-sorted COO  base/torch_interface.py:8-12
@@ -339,6 +341,45 @@ hgd_status hgd_spmm_ordered(const int64_t* rowptr, const int32_t* col, const flo
                             float* Y, int64_t ldy, int32_t d, int32_t epilogue, float slope,
                             const hgd_split_plan* plan, void* workspace, size_t workspace_bytes,
                             const int32_t* out_row, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * hgd_spmm_blocked (every row, fp32) with the rows of EACH SOURCE BLOCK walked in ascending order
+ * of the first (smallest) column they have in that block: the two ideas above together, so that
+ * the first gather of most row pieces of a pass is an L2 hit. Replaces the same call sites as
+ * hgd_spmm_blocked (torch.sparse.mm(adj.t(), X), model/graph/HGNN_HD4.py:459-462). Each piece is
+ * the same fmaf chain in edge order and block k's partial is added to Y in the same block order,
+ * so Y is bitwise hgd_spmm_blocked's.
+ *
+ * hgd_spmm_col_blocks_ordered builds what hgd_spmm_col_blocks builds with block k's pieces laid
+ * out in that order (a row without a nonzero in block k counts as n_cols and sorts last; ties in
+ * natural row order, hgd_sort_perm is stable):
+ *   blk_start:   int64 [n_blocks·n_rows + 1], the piece at POSITION p of block k is
+ *                [blk_start[k·n_rows + p], blk_start[k·n_rows + p + 1]) of blk_col; closed by nnz
+ *   blk_out_row: int32 [n_blocks·n_rows], the row position p of block k holds — gather per-row
+ *                scales through it (hgd_gather32) to get hgd_spmm_blocked_ordered's blk_row_scale
+ *   blk_col, blk_perm (may be NULL): as hgd_spmm_col_blocks'; a piece's columns keep their order
+ * blk_col doubles as the builder's scratch. No atomics, stream-ordered, no host synchronisation.
+ * Workspace: hgd_spmm_col_blocks_ordered_workspace_size.
+ *
+ * hgd_spmm_blocked_ordered: blk_row_scale is [n_blocks·n_rows] in processing order, or NULL.
+ * Inside the library a mask, a fused row epilogue, a split plan and a row range stay refused
+ * (HGD_ERR_UNSUPPORTED); the entry point takes none of them.
+ * ---------------------------------------------------------------------------------------- */
+/* The size rule both hosts use: 1 when a hop of nnz nonzeros over n_rows rows
+ * gathering n_src_rows rows at width d in n_blocks source blocks should order each block. */
+int32_t hgd_spmm_block_order_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz, int32_t d,
+                                 int32_t n_blocks);
+size_t hgd_spmm_col_blocks_ordered_workspace_size(int64_t n_rows, int32_t n_blocks);
+hgd_status hgd_spmm_col_blocks_ordered(const int64_t* rowptr, const int32_t* col, int64_t n_rows,
+                                       int64_t n_cols, int32_t n_blocks, int64_t* blk_start,
+                                       int32_t* blk_col, int32_t* blk_perm, int32_t* blk_out_row,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+hgd_status hgd_spmm_blocked_ordered(const int64_t* blk_start, const int32_t* blk_col,
+                                    const float* blk_val, const float* blk_row_scale,
+                                    const int32_t* blk_out_row, int64_t n_rows,
+                                    int64_t n_src_rows, const float* X, int64_t ldx, float* Y,
+                                    int64_t ldy, int32_t d, int32_t epilogue, float slope,
+                                    int32_t n_blocks, void* stream);
 
 /* The same hop over the EDGE-DROPPED matrix of SpAdjDropEdge (model/graph/HCCF.py:213-226:
  * mask = floor(rand + keepRate), idxs[:, mask], vals[mask] / keepRate) without building it: the

@@ -16,7 +16,14 @@ summation order, so not bitwise).
 the min–max spread of the rounds, and TB/s on the variant's own algorithmic bytes
 (profiling.hop_bytes with its element sizes).
 
+--block-order on|both times the fp32 blocked hop over per-block row orders
+(hgd_spmm_blocked_ordered over hgd_spmm_col_blocks_ordered, selected through
+HGD_SPMM_BLOCK_ORDER) instead of, or interleaved with, hgd_spmm_blocked, and checks that the two
+outputs are bitwise equal; with `both` the default block counts are 3,4,5,6, so that a shift of
+the best P shows.
+
     python scripts/bench_mall_blocked.py [--dim 64 --rounds 5 --table-dtype bf16]
+    python scripts/bench_mall_blocked.py --block-order both [--dim 128 --blocks 6,8,10]
 """
 import argparse
 import json
@@ -35,7 +42,11 @@ def main():
     ap.add_argument("--edges", type=int, default=100_000_000)
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--blocks", default="2,4,8,10,16")
+    ap.add_argument("--blocks", default=None,
+                    help="block counts (default 2,4,8,10,16; 3,4,5,6 with --block-order both)")
+    ap.add_argument("--block-order", choices=("off", "on", "both"), default="off",
+                    help="each source block's rows in ascending order of their first column "
+                         "(fp32 only): off, on, or both interleaved and compared bitwise")
     ap.add_argument("--hop", choices=("items", "users"), default="items",
                     help="items: Hᵀ·X over the CSC (gathers the user table); users: H·M over the "
                          "CSR (gathers the item table)")
@@ -95,38 +106,62 @@ def main():
     if x_dtype != torch.float32:
         # (a column slice stays one: the wide table is converted, then cut again)
         X = X.to(x_dtype) if X._base is None else X._base.to(x_dtype)[:, :d]
-    blocks = [int(p) for p in args.blocks.split(",")]
-    for P in blocks:  # block-major copies built outside the timed rounds
-        S.col_blocks(P)
-        S.blocked_values(P, w_full)
+    if args.block_order != "off" and (x_dtype, y_dtype) != (torch.float32, torch.float32):
+        ap.error("--block-order needs an fp32 table and output")
+    default_blocks = "3,4,5,6" if args.block_order == "both" else "2,4,8,10,16"
+    counts = [int(p) for p in (args.blocks or default_blocks).split(",")]
+    orders = {"off": ["0"], "on": ["1"], "both": ["0", "1"]}[args.block_order]
+    # a variant: (P, HGD_SPMM_BLOCK_ORDER); its key in the output is P, or P+ord with the order
+    blocks = [(P, o) for P in counts for o in orders]
+    name = {(P, o): f"{P}+ord" if o == "1" else P for P, o in blocks}
+    for P, o in blocks:  # block-major copies built outside the timed rounds
+        if o == "1":
+            S.col_blocks_ordered(P)
+            S.blocked_ordered_values(P, w_full)
+            S.blocked_ordered_scale(P, q)
+        else:
+            S.col_blocks(P)
+            S.blocked_values(P, w_full)
 
-    def run(P):
-        # HGD_SPMM_BLOCKS=0: hgd_spmm; =P: hgd_spmm_blocked over P source ranges (spmm_blocks)
+    def run(P, order="0"):
+        # HGD_SPMM_BLOCKS=0: hgd_spmm; =P: hgd_spmm_blocked over P source ranges (spmm_blocks),
+        # with HGD_SPMM_BLOCK_ORDER=1 hgd_spmm_blocked_ordered
         os.environ["HGD_SPMM_BLOCKS"] = str(P)
+        os.environ["HGD_SPMM_BLOCK_ORDER"] = order
         return spmm_csr(S, X, val=w_full, row_scale=q, out_dtype=y_dtype)
 
     ref = run(0).float()
     res = {"dim": d, "hop": args.hop, "pass_cols": args.pass_cols, "policy": args.policy, "unroll": args.unroll, "seg": args.seg, "ld": args.ld, "nnz": nnz,
            "table_dtype": args.table_dtype, "out_dtype": args.out_dtype or args.table_dtype,
-           "rounds": args.rounds,
+           "rounds": args.rounds, "block_order": args.block_order,
            "bytes_algorithmic": profiling.hop_bytes(nnz, R, d, x_bytes=X.element_size(),
                                                     y_bytes=4 if y_dtype == torch.float32 else 2),
            "variants": {}}
     times = {"plain": []}
-    times.update({P: [] for P in blocks})
+    times.update({name[v]: [] for v in blocks})
     diffs = {}
+    bitwise = {}  # P -> the ordered hop's output equals hgd_spmm_blocked's bit for bit
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     for rnd in range(args.rounds + 1):
-        for key in ["plain"] + blocks:
+        kept = {}  # (first round, both) P -> hgd_spmm_blocked's output
+        for v in ["plain"] + blocks:
+            key = v if v == "plain" else name[v]
             ev[0].record()
-            Y = run(0 if key == "plain" else key)
+            Y = run(0) if v == "plain" else run(*v)
             ev[1].record()
             torch.cuda.synchronize()
             if rnd:
                 times[key].append(ev[0].elapsed_time(ev[1]))
-            elif key != "plain":
+            elif v != "plain":
                 diffs[key] = float((Y.float() - ref).abs().max() / ref.abs().max())
+                if args.block_order == "both" and v[1] == "0":
+                    kept[v[0]] = Y
+                elif args.block_order == "both":
+                    bitwise[v[0]] = bool(torch.equal(Y, kept.pop(v[0])))
             del Y
+    if bitwise:
+        res["ordered_bitwise_equal"] = {str(P): ok for P, ok in bitwise.items()}
+        print("ordered output bitwise equal to hgd_spmm_blocked's:", bitwise, flush=True)
     for key, ts in times.items():
         ms = statistics.median(ts)
         res["variants"][str(key)] = {"ms": round(ms, 4), "ms_min": round(min(ts), 4),
@@ -137,6 +172,8 @@ def main():
         print(f"{str(key):6s} {ms:8.3f} ms (min {min(ts):.3f}, max {max(ts):.3f})  "
               f"{res['bytes_algorithmic'] / ms / 1e9:6.3f} TB/s", flush=True)
     print(json.dumps(res), flush=True)
+    if not all(bitwise.values()):
+        sys.exit("the ordered hop's output differs from hgd_spmm_blocked's")
 
 
 if __name__ == "__main__":
