@@ -464,6 +464,17 @@ _SIGNATURES = {
         c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_i64, c_f32, c_i64,
         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size,
         c_void_p]),
+    # view attention (KHGRec's fusion of the two item views)
+    "hgd_view_attention_row_block": (c_i32, []),
+    "hgd_view_attention_workspace_size": (c_size, [c_i64, c_i32, c_i64, c_i64]),
+    "hgd_view_attention_forward": (c_i32, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i32,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                           c_void_p, c_i64, c_void_p]),
+    "hgd_view_attention_backward": (c_i32, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i32,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                            c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size,
+                                            c_void_p]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@ GCNLayer               model/graph/HCCF.py:193-199                      hgd_spmm
 HGNNLayer              model/graph/HCCF.py:201-211                      hgd_linear_* (f32 MFMA)
 HGCNConv               model/graph/HGNN_HD4.py:450-462 (and copies)     2 hops, fused LeakyReLU
 AttHGCNConv            model/graph/KHGRec.py:440-453                    4 hops, fused LeakyReLU
+Attention              model/graph/KHGRec.py:466-480 (and copies)       hgd_view_attention_*
 SpAdjDropEdge          model/graph/HCCF.py:213-226                      hgd_dropedge_compact
 EquivSetConv           model/layers/layers2/EquivSetConv2.py:38-100     mean/sum 2-hop (V/E)
 EquivSetGNN            model/layers/layers2/EquivSetGNN2.py:32-155      hgd_dense_threshold_*
@@ -39,6 +40,7 @@ from .functional import (att_two_hop, dense_mean_two_hop, dense_mean_two_hop_ok,
                          two_hop_fused)
 from .incidence import (CSR, Incidence, MaskedIncidence, dense_threshold, drop_edges,
                         expand_rows, incidence_of)
+from .view_attention import view_attention_stacked
 
 
 class GCNLayer(nn.Module):
@@ -107,6 +109,40 @@ class AttHGCNConv(nn.Module):
 
 
 _NATIVE_CPU_MASK: Optional[bool] = None
+
+
+class Attention(nn.Module):
+    """The view fusion of KHGRec.py:466-480 (the same class in HGNN_cp.py and HGNNAblation.py)
+    with the reference's constructor and parameter names (``project.0.weight``,
+    ``project.0.bias``, ``project.2.weight``: a reference ``state_dict`` loads). ``forward(z)``
+    takes the stacked ``[N, 2, d]`` tensor and returns ``(fused, beta)``; on the device at a fused
+    width it is one kernel forward and one backward (:func:`~.view_attention.view_attention`),
+    anything else runs the reference's expression. ``beta`` carries no gradient (the reference's
+    callers discard it); ``need_beta=False`` returns ``None`` in its place and skips building
+    it. The two-tensor call without the stack is ``view_attention(z0, z1, *attention.weights())``.
+    """
+
+    def __init__(self, in_size, hidden_size=128, need_beta=True):
+        super().__init__()
+        if hidden_size != in_size:
+            raise ValueError(f"Attention: hidden_size = {hidden_size} must equal in_size = "
+                             f"{in_size}: the reference's (beta * z).sum(1) broadcasts beta "
+                             f"[N, 2, hidden_size] against z [N, 2, in_size]")
+        self.need_beta = bool(need_beta)
+        self.project = nn.Sequential(
+            nn.Linear(in_size, hidden_size),
+            nn.Tanh(),
+            nn.Linear(hidden_size, hidden_size, bias=False),
+        )
+
+    def weights(self):
+        """``(weight1, bias1, weight2)`` as :func:`~.view_attention.view_attention` takes them."""
+        return self.project[0].weight, self.project[0].bias, self.project[2].weight
+
+    def forward(self, z):
+        if self.need_beta:
+            return view_attention_stacked(z, *self.weights(), return_beta=True)
+        return view_attention_stacked(z, *self.weights()), None
 
 
 def _native_cpu_mask_ok() -> bool:

@@ -1347,6 +1347,51 @@ hgd_status hgd_kg_loss_backward(const float* xh, int64_t ldh, const int32_t* ih,
                                 float* dR, void* workspace, size_t workspace_bytes,
                                 void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * View attention: KHGRec's fusion of an item's two views, Attention.forward of
+ * model/graph/KHGRec.py:466-480, called at :132 (every minibatch) and :202 (every evaluation)
+ * on torch.stack([item_emb_cf, item_emb_kg], dim=1). With two views z0, z1 [n_rows, d] and
+ * W1 [d, d], b1 [d], W2 [d, d] (nn.Linear.weight layout, contiguous; hidden_size == in_size):
+ *   t_v = tanh(z_v·W1ᵀ + b1);  q = (t_0 − t_1)·W2ᵀ;  β0 = σ(q);  out = β0 ⊙ z0 + (1 − β0) ⊙ z1
+ * (σ(q) is the softmax over the two views of w_v = t_v·W2ᵀ, view 0; it is taken from one
+ * exponential of −|q| and is finite for every finite q.)
+ *   dq = g ⊙ (z0 − z1) ⊙ β0(1 − β0);  h = dq·W2;  da_0 = h ⊙ (1 − t_0²);  da_1 = −h ⊙ (1 − t_1²)
+ *   dz_v = β_v ⊙ g + da_v·W1;  dW2 = dqᵀ·(t_0 − t_1);  dW1 = da_0ᵀ·z0 + da_1ᵀ·z1;
+ *   db1 = Σ_rows (da_0 + da_1)           (β as a returned value carries no gradient)
+ * d: a multiple of 16 in [16, 128]. Every row operand (z0, z1, out, beta0, g, dz0, dz1) is a
+ * pointer and a leading dimension >= d with 16-byte aligned rows (pointer % 16 == 0, ld % 4 ==
+ * 0): the two halves of a stacked [n_rows, 2, d] tensor are read and written in place with
+ * ld = 2d. One workgroup owns hgd_view_attention_row_block() = 32 rows; the products run as
+ * split-bf16 MFMAs (error ≈ 1e-7·Σ|a·b|) with the weights' fragments in registers. A row's
+ * results depend on that row alone (not on n_rows or its position); no float atomics: two runs
+ * are bitwise equal. n_rows = 0 validates, launches nothing and writes nothing.
+ *
+ * hgd_view_attention_forward — one kernel; writes out, and beta0 (β0 [n_rows, d]) unless it is
+ *   NULL (evaluation / no_grad). No [n_rows, 2, d] intermediate reaches memory.
+ * hgd_view_attention_backward — one kernel recomputes t_v and writes dz0, dz1 (both or neither;
+ *   NULL = not computed). dW1, db1, dW2 (all or none; contiguous [d, d], [d], [d, d], written
+ *   in full): the kernel also stores dq, t_0 − t_1, da_0, da_1 to the workspace and two
+ *   hgd_gemm_tn calls reduce them over the rows (split-K, slices summed in slice order).
+ *   Without them no workspace is read and nothing but dz0, dz1 is stored.
+ * Workspace: hgd_view_attention_workspace_size(n_rows, d, ld0, ld1) for the backward with
+ *   parameter gradients (4·n_rows·d floats + hgd_gemm_tn's partials); 16-byte aligned; 0 for
+ *   n_rows = 0. Every argument is checked before the first HIP call (HGD_ERR_INVALID_ARG: a
+ *   width that is not fused, misaligned rows, ld < d, a required pointer NULL, a workspace too
+ *   small). Stream-ordered, no host synchronisation, no allocation. */
+int32_t hgd_view_attention_row_block(void);
+size_t hgd_view_attention_workspace_size(int64_t n_rows, int32_t d, int64_t ld0, int64_t ld1);
+hgd_status hgd_view_attention_forward(const float* z0, int64_t ld0, const float* z1, int64_t ld1,
+                                      int64_t n_rows, int32_t d, const float* W1,
+                                      const float* b1, const float* W2, float* out, int64_t ldo,
+                                      float* beta0, int64_t ldb, void* stream);
+hgd_status hgd_view_attention_backward(const float* z0, int64_t ld0, const float* z1,
+                                       int64_t ld1, int64_t n_rows, int32_t d, const float* W1,
+                                       const float* b1, const float* W2, const float* beta0,
+                                       int64_t ldb, const float* g, int64_t ldg, float* dz0,
+                                       int64_t lddz0, float* dz1, int64_t lddz1, float* dW1,
+                                       float* db1, float* dW2, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

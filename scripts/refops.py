@@ -103,6 +103,16 @@ def kg_loss_ref(h_embed, r, pos_t_embed, neg_t_embed, trans_M, relation_emb, reg
     return loss + sum(torch.norm(x, p=2) for x in (a, e, p, n)) * reg_kg / batch_size_kg
 
 
+def view_attention_ref(z, weight1, bias1, weight2):
+    """What KHGRec's Attention.forward computes on the stacked [N, 2, d] views (KHGRec.py:
+    477-480; the caller's torch.stack of :132 / :202 is the bench's to add), with the same torch
+    ops: Linear, Tanh, the bias-free Linear, the softmax over the two views and the weighted sum.
+    Returns (fused, beta) as the reference does."""
+    w = F.linear(torch.tanh(F.linear(z, weight1, bias1)), weight2)
+    beta = torch.softmax(w, dim=1)
+    return (beta * z).sum(1), beta
+
+
 def contrast_loss(embeds1, embeds2, nodes, temp):
     """contrastLoss (util/loss_torch.py:103-110)."""
     embeds1 = F.normalize(embeds1 + 1e-8, p=2)
