@@ -12,6 +12,7 @@ with the reference's operator signatures:
 * :mod:`.kg_attention` — KHGRec's per-batch KG attention (triple scores, row softmax) on device
 * :mod:`.kg_loss`    — KHGRec's TransR KG loss, fused forward and backward (no [B, d, dr] gather)
 * :mod:`.view_attention` — KHGRec's fusion of the two item views, one kernel each way
+* :mod:`.cf_loss`    — KHGRec's CF loss (fusion + BPR + regulariser) over the batch's item rows only
 * :mod:`.sharded`    — user-row sharding across GPUs with an RCCL all-reduce of hyperedge sums
 """
 from . import _native
@@ -21,9 +22,11 @@ from .functional import (att_two_hop, att_two_hop_fused, contrast_loss, hgconv2,
 from .kg_attention import KGAttentionPattern, kg_attention
 from .kg_loss import kg_loss, kg_loss_rows
 from .view_attention import view_attention, view_attention_stacked, view_attention_supported
+from .cf_loss import cf_loss, cf_loss_supported
 
 __all__ = ["CSR", "Incidence", "incidence_of", "spmm_csr", "spmm", "two_hop", "hgconv2",
            "mean2hop", "contrast_loss", "unique_long", "att_two_hop", "att_two_hop_fused",
            "KGAttentionPattern", "kg_attention", "kg_loss", "kg_loss_rows", "view_attention",
-           "view_attention_stacked", "view_attention_supported", "_native"]
+           "view_attention_stacked", "view_attention_supported", "cf_loss", "cf_loss_supported",
+           "_native"]
 __version__ = "0.1.0"

@@ -216,6 +216,10 @@ SIDE_ROWS, SIDE_COLS = 0, 1
 COMM_ID_BYTES = 128
 P2P_HANDLE_BYTES = 4096
 _PP = ctypes.POINTER(c_void_p)
+# hgd_cf_loss_*: U, ldu, uid, n_users, Z0, ld0, Z1, ld1, pid, nid, n_items, batch, d, W1, b1, W2,
+# reg, batch_size
+_CF_LOSS_IN = [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
+               c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_f32, c_i64]
 
 # name -> (restype, argtypes); every symbol of include/hgd.h appears here.
 _SIGNATURES = {
@@ -475,6 +479,13 @@ _SIGNATURES = {
                                             c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size,
                                             c_void_p]),
+    # CF loss (KHGRec's view fusion + BPR + regulariser over the batch's item rows only)
+    "hgd_cf_loss_workspace_size": (c_size, [c_i64, c_i32, c_i32]),
+    "hgd_cf_loss_forward": (c_i32, _CF_LOSS_IN + [
+        c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "hgd_cf_loss_backward": (c_i32, _CF_LOSS_IN + [
+        c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64,
+        c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
 }
 
 _lib = None

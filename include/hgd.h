@@ -1392,6 +1392,67 @@ hgd_status hgd_view_attention_backward(const float* z0, int64_t ld0, const float
                                        float* db1, float* dW2, void* workspace,
                                        size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CF loss: KHGRec's recommendation loss of a minibatch (model/graph/KHGRec.py:131-143 and
+ * calculate_cf_loss, :341-345) with the view fusion evaluated ONLY at the batch's item rows.
+ * U [n_users, d] user rows; Z0, Z1 [n_items, d] the items' two views; uid, pid, nid [batch]
+ * int32 ids (assumed in range: hgd_index_narrow checks them); W1, b1, W2 the Attention's
+ * parameters as for the view attention, or all three NULL for the mean of the views
+ * (KHGRec.py:134). Item position p in [0, 2·batch) is INTERLEAVED: p = 2k is triple k's
+ * positive, p = 2k + 1 its negative (a 32-row block holds 16 whole triples):
+ *   i_p  = p even ? pid[p/2] : nid[p/2]
+ *   F_p  = β0 ⊙ Z0[i_p] + (1 − β0) ⊙ Z1[i_p]   (β0 as in "View attention"; mean mode: β0 = 1/2)
+ *   a_k  = U[uid[k]];   x_k = <a_k, F_2k> − <a_k, F_2k+1>
+ *   loss = (1/batch) Σ_k −log(1e-5 + σ(x_k)) + reg · (‖A‖_F + ‖P‖_F + ‖N‖_F) / batch_size
+ * A, P, N the gathered [batch, d] matrices (a repeated row counts once per occurrence; the norms
+ * are not squared, util/loss_torch.py:17-21). The mean divides by batch, the regulariser by the
+ * configured batch_size. With g = *grad and c_k = σ(x)σ(−x)/(1e-5 + σ(x)) (coef):
+ *   dF_2k   = −(g/batch)·c_k·a_k + (g·reg/batch_size)·F_2k/‖P‖
+ *   dF_2k+1 = +(g/batch)·c_k·a_k + (g·reg/batch_size)·F_2k+1/‖N‖
+ *   da_k    = −(g/batch)·c_k·(F_2k − F_2k+1) + (g·reg/batch_size)·a_k/‖A‖
+ * (a norm that is exactly 0 contributes a 0 gradient), and dZ0, dZ1, dW1, db1, dW2 follow from dF
+ * by the view attention's backward at the 2·batch positions (mean mode: dZ0 = dZ1 = dF/2).
+ * d: a multiple of 16 in [16, 128] with parameters, a multiple of 4 in [4, 256] in mean mode.
+ * Row operands are a pointer and a leading dimension >= d with 16-byte aligned rows. Work and
+ * memory are O(batch·d): F and dF stay on chip, the views are read through the ids. fp32, every
+ * sum in a fixed order, no float atomics: two runs are bitwise equal, and coef[k] and the
+ * gradients of triple k depend on that triple's rows and on the three norms alone.
+ *
+ * hgd_cf_loss_forward — one row kernel (a workgroup owns 32 positions) and a single-workgroup
+ *   kernel that adds the blocks' partial sums in block order. Writes coef [batch],
+ *   norms [3] = (‖A‖, ‖P‖, ‖N‖), loss [1], and beta0 [2·batch, d] unless it is NULL (no backward
+ *   to follow; it must be NULL in mean mode).
+ * hgd_cf_loss_backward — one row kernel. dA [batch, d] (NULL = not computed), dZ0 / dZ1
+ *   [2·batch, ·] per POSITION (both or neither), dW1, db1, dW2 (all or none, written in full; the
+ *   kernel then also stores six [2·batch, d] operands to the workspace and hgd_gemm_tn reduces
+ *   them). The fold of dA and dZ into [n_users, d] / [n_items, d] tables — the sum over the
+ *   positions of each row, in ascending position order — is the CALLER's hop (an SpMM with the
+ *   binary matrix "row ← position"; the Python host uses hgd_sort_perm + hgd_spmm).
+ * Workspace: hgd_cf_loss_workspace_size(batch, d, with_params): the forward needs
+ *   (batch, d, 0), the backward (batch, d, 1) when parameter gradients are asked for and none
+ *   otherwise; 16-byte aligned. 0 for batch <= 0 or a width outside the mode's set. Every
+ *   argument is checked before the first HIP call (HGD_ERR_INVALID_ARG; HGD_ERR_WORKSPACE for a
+ *   workspace that is NULL or too small). batch = 0 validates and launches nothing.
+ *   Stream-ordered, no host synchronisation, no allocation. */
+size_t hgd_cf_loss_workspace_size(int64_t batch, int32_t d, int32_t with_params);
+hgd_status hgd_cf_loss_forward(const float* U, int64_t ldu, const int32_t* uid, int64_t n_users,
+                               const float* Z0, int64_t ld0, const float* Z1, int64_t ld1,
+                               const int32_t* pid, const int32_t* nid, int64_t n_items,
+                               int64_t batch, int32_t d, const float* W1, const float* b1,
+                               const float* W2, float reg, int64_t batch_size, float* beta0,
+                               int64_t ldb, float* coef, float* norms, float* loss,
+                               void* workspace, size_t workspace_bytes, void* stream);
+hgd_status hgd_cf_loss_backward(const float* U, int64_t ldu, const int32_t* uid, int64_t n_users,
+                                const float* Z0, int64_t ld0, const float* Z1, int64_t ld1,
+                                const int32_t* pid, const int32_t* nid, int64_t n_items,
+                                int64_t batch, int32_t d, const float* W1, const float* b1,
+                                const float* W2, float reg, int64_t batch_size,
+                                const float* beta0, int64_t ldb, const float* coef,
+                                const float* norms, const float* grad, float* dA, int64_t ldda,
+                                float* dZ0, int64_t lddz0, float* dZ1, int64_t lddz1, float* dW1,
+                                float* db1, float* dW2, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

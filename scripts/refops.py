@@ -113,6 +113,27 @@ def view_attention_ref(z, weight1, bias1, weight2):
     return (beta * z).sum(1), beta
 
 
+def cf_loss_ref(user_emb, item_cf, item_kg, uid, pid, nid, reg, batch_size, weight1=None,
+                bias1=None, weight2=None):
+    """What KHGRec's training step computes for its CF loss (KHGRec.py:131-143, :341-345), with
+    the same torch ops in the same places: the stack and the fusion over EVERY item (the Attention,
+    or the mean of the two views when no weights are given), the three gathers, bpr_loss and
+    l2_reg_loss (util/loss_torch.py:5-9, :17-21) divided by the configured batch size."""
+    z = torch.stack([item_cf, item_kg], dim=1)
+    if weight1 is not None:
+        fused, _ = view_attention_ref(z, weight1, bias1, weight2)
+    else:
+        fused = torch.mean(z, dim=1)
+    anchor, pos, neg = user_emb[uid], fused[pid], fused[nid]
+    pos_score = torch.mul(anchor, pos).sum(dim=1)
+    neg_score = torch.mul(anchor, neg).sum(dim=1)
+    loss = torch.mean(-torch.log(10e-6 + torch.sigmoid(pos_score - neg_score)))
+    emb_loss = 0
+    for emb in (anchor, pos, neg):
+        emb_loss += torch.norm(emb, p=2)
+    return loss + emb_loss * reg / batch_size
+
+
 def contrast_loss(embeds1, embeds2, nodes, temp):
     """contrastLoss (util/loss_torch.py:103-110)."""
     embeds1 = F.normalize(embeds1 + 1e-8, p=2)
