@@ -13,6 +13,8 @@ with the reference's operator signatures:
 * :mod:`.kg_loss`    — KHGRec's TransR KG loss, fused forward and backward (no [B, d, dr] gather)
 * :mod:`.view_attention` — KHGRec's fusion of the two item views, one kernel each way
 * :mod:`.cf_loss`    — KHGRec's CF loss (fusion + BPR + regulariser) over the batch's item rows only
+* :mod:`.ingest`     — ``InteractionGraph`` / ``KnowledgeGraph``: the loaders' matrices and tables on device
+* :mod:`.sampler`    — the reference's pairwise and unified (CF + KG) batches, bit for bit, in libhgd
 * :mod:`.sharded`    — user-row sharding across GPUs with an RCCL all-reduce of hyperedge sums
 """
 from . import _native
@@ -23,8 +25,9 @@ from .kg_attention import KGAttentionPattern, kg_attention
 from .kg_loss import kg_loss, kg_loss_rows
 from .view_attention import view_attention, view_attention_stacked, view_attention_supported
 from .cf_loss import cf_loss, cf_loss_supported
+from .ingest import InteractionGraph, KnowledgeGraph
 
-__all__ = ["CSR", "Incidence", "incidence_of", "spmm_csr", "spmm", "two_hop", "hgconv2",
+__all__ = ["InteractionGraph", "KnowledgeGraph","CSR", "Incidence", "incidence_of", "spmm_csr", "spmm", "two_hop", "hgconv2",
            "mean2hop", "contrast_loss", "unique_long", "att_two_hop", "att_two_hop_fused",
            "KGAttentionPattern", "kg_attention", "kg_loss", "kg_loss_rows", "view_attention",
            "view_attention_stacked", "view_attention_supported", "cf_loss", "cf_loss_supported",

@@ -192,6 +192,21 @@ class MaskedSum(ctypes.Structure):
                 ("count", c_i32), ("scale", c_f32)]
 
 
+class UnifiedBatch(ctypes.Structure):
+    """Mirror of ``hgd_unified_batch`` (include/hgd.h)."""
+
+    _fields_ = [("py_state", c_void_p), ("np_state", c_void_p), ("order", c_void_p),
+                ("begin", c_i64), ("end", c_i64), ("rec_user", c_void_p), ("rec_item", c_void_p),
+                ("user_rowptr", c_void_p), ("user_items", c_void_p), ("n_users", c_i64),
+                ("n_items", c_i64), ("n_negs", c_i32), ("reserved", c_i32),
+                ("sel_head", c_void_p), ("sel_rel", c_void_p), ("sel_tail", c_void_p),
+                ("n_sel", c_i64), ("head_ids", c_void_p), ("all_tails", c_void_p),
+                ("n_tails", c_i64), ("tail_rowptr", c_void_p), ("tail_sorted", c_void_p),
+                ("n_heads", c_i64), ("batch_kg", c_i64), ("out_u", c_void_p),
+                ("out_i", c_void_p), ("out_j", c_void_p), ("out_h", c_void_p),
+                ("out_r", c_void_p), ("out_t", c_void_p), ("out_n", c_void_p)]
+
+
 class IncidenceView(ctypes.Structure):
     """Mirror of ``hgd_incidence_view`` (include/hgd.h)."""
 
@@ -374,6 +389,11 @@ _SIGNATURES = {
     "hgd_sample_pairwise": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p,
                                     c_void_p]),
+    "hgd_py_shuffle_rows": (c_i32, [c_void_p, c_void_p, c_i64]),
+    "hgd_sample_unified": (c_i32, [c_void_p]),
+    "hgd_kg_expand": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p]),
     "hgd_torch_cpu_state_bytes": (c_size, []),
     "hgd_torch_cpu_jump_selfcheck": (c_i32, [c_i64]),
     "hgd_torch_cpu_keep_mask": (c_i32, [c_void_p, c_i64, c_i64, c_f32, c_void_p,

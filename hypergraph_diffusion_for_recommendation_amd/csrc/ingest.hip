@@ -241,6 +241,98 @@ __global__ void k_normalize_values(const int64_t* __restrict__ rowptr,
   }
 }
 
+// ---- Knowledge.construct_data (data/knowledge.py:44-72)
+// stats: [0] = max(h, t) + 1, [1] = max over h, t and the CF ids + 1, [2] = max(r) + 1,
+// [3] = ids a later int32 narrowing (or the r + n0 + 2 shift) could not hold. Integer atomics
+// only, one per wave and statistic; the maxima of an empty input stay 0.
+constexpr int64_t kKgIdLimit = 0x7ffffffeLL;   // ids < this: n_rows = id + 1 < 2^31 - 1
+constexpr int64_t kKgRelLimit = 0x3fffffffLL;  // 2·(r + 1) + 2 stays an int32
+
+__device__ inline unsigned long long wave_max_u64(unsigned long long v) {
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long o = __shfl_xor(v, m, 64);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+__global__ void k_kg_stats(const int64_t* __restrict__ h, const int64_t* __restrict__ r,
+                           const int64_t* __restrict__ t, int64_t n,
+                           const int64_t* __restrict__ cf_u, const int64_t* __restrict__ cf_i,
+                           int64_t n_cf, unsigned long long* __restrict__ stats) {
+  unsigned long long ent = 0, all = 0, rel = 0, bad = 0;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+  const int64_t tid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  for (int64_t i = tid; i < n; i += stride) {
+    const int64_t a = h[i], b = t[i], c = r[i];
+    if (a < 0 || a >= kKgIdLimit || b < 0 || b >= kKgIdLimit || c < 0 || c >= kKgRelLimit) {
+      ++bad;
+      continue;
+    }
+    const unsigned long long e = static_cast<unsigned long long>(a > b ? a : b) + 1;
+    ent = e > ent ? e : ent;
+    rel = static_cast<unsigned long long>(c) + 1 > rel ? static_cast<unsigned long long>(c) + 1
+                                                       : rel;
+  }
+  all = ent;
+  for (int64_t i = tid; i < n_cf; i += stride) {
+    const int64_t a = cf_u[i], b = cf_i[i];
+    if (a < 0 || a >= kKgIdLimit || b < 0 || b >= kKgIdLimit) {
+      ++bad;
+      continue;
+    }
+    const unsigned long long e = static_cast<unsigned long long>(a > b ? a : b) + 1;
+    all = e > all ? e : all;
+  }
+  ent = wave_max_u64(ent);
+  all = wave_max_u64(all);
+  rel = wave_max_u64(rel);
+  for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
+  if ((threadIdx.x & 63) == 0) {
+    if (ent) atomicMax(stats + 0, ent);
+    if (all) atomicMax(stats + 1, all);
+    if (rel) atomicMax(stats + 2, rel);
+    if (bad) atomicAdd(stats + 3, bad);
+  }
+}
+
+// The five blocks of kg_train_data in the reference's order, n0 = stats[2] = max(r) + 1:
+// (h, r+2, t) | (t, r+n0+2, h) | (t, r+n0, h) | (u, 0, i) | (i, 1, u). The int32 copies feed the
+// sorts (they are only used after the host has seen stats[3] == 0).
+__global__ void k_kg_expand(const int64_t* __restrict__ h, const int64_t* __restrict__ r,
+                            const int64_t* __restrict__ t, int64_t n,
+                            const int64_t* __restrict__ cf_u, const int64_t* __restrict__ cf_i,
+                            int64_t n_cf, const int64_t* __restrict__ stats,
+                            int64_t* __restrict__ h_out, int64_t* __restrict__ r_out,
+                            int64_t* __restrict__ t_out, int32_t* __restrict__ h32,
+                            int32_t* __restrict__ r32, int32_t* __restrict__ t32) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= 3 * n + 2 * n_cf) return;
+  const int64_t n0 = stats[2];
+  int64_t a, b, c;
+  if (i < 3 * n) {
+    const int64_t blk = i / n, k = i - blk * n;
+    if (blk == 0) {
+      a = h[k], b = r[k] + 2, c = t[k];
+    } else {
+      a = t[k], b = r[k] + n0 + (blk == 1 ? 2 : 0), c = h[k];
+    }
+  } else {
+    const int64_t j = i - 3 * n;
+    const bool inv = j >= n_cf;
+    const int64_t k = inv ? j - n_cf : j;
+    a = inv ? cf_i[k] : cf_u[k];
+    b = inv ? 1 : 0;
+    c = inv ? cf_u[k] : cf_i[k];
+  }
+  h_out[i] = a;
+  r_out[i] = b;
+  t_out[i] = c;
+  h32[i] = static_cast<int32_t>(a);
+  r32[i] = static_cast<int32_t>(b);
+  t32[i] = static_cast<int32_t>(c);
+}
+
 int bits_for(int64_t n) {
   int b = 1;
   while (b < 63 && (1LL << b) < n) ++b;
@@ -544,4 +636,35 @@ extern "C" hgd_status hgd_normalize_values(const int64_t* rowptr, const int32_t*
   hipLaunchKernelGGL(k_normalize_values, dim3(grid_for(n_rows)), dim3(kBlock), 0,
                      as_stream(stream), rowptr, col, val, n_rows, row_scale, col_scale, out);
   return check_launch("hgd_normalize_values");
+}
+
+extern "C" hgd_status hgd_kg_expand(const int64_t* h, const int64_t* r, const int64_t* t,
+                                    int64_t n, const int64_t* cf_u, const int64_t* cf_i,
+                                    int64_t n_cf, int64_t* h_out, int64_t* r_out, int64_t* t_out,
+                                    int32_t* h32_out, int32_t* r32_out, int32_t* t32_out,
+                                    int64_t* stats, void* stream) {
+  using namespace hgd;
+  clear_error();
+  HGD_REQUIRE(n >= 0 && n_cf >= 0, "hgd_kg_expand: negative count");
+  HGD_REQUIRE(n < 0x7fffffffLL / 3 && n_cf < 0x7fffffffLL / 4 && 3 * n + 2 * n_cf < 0x7fffffffLL,
+              "hgd_kg_expand: 3n + 2n_cf out of range");
+  HGD_REQUIRE(stats, "hgd_kg_expand: null stats");
+  HGD_REQUIRE((n == 0 || (h && r && t)) && (n_cf == 0 || (cf_u && cf_i)),
+              "hgd_kg_expand: null input");
+  hipStream_t st = as_stream(stream);
+  HGD_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), st));
+  const int64_t total = 3 * n + 2 * n_cf;
+  if (total == 0) return HGD_OK;
+  HGD_REQUIRE(h_out && r_out && t_out && h32_out && r32_out && t32_out,
+              "hgd_kg_expand: null output");
+  const int64_t widest = n > n_cf ? n : n_cf;
+  unsigned blocks = grid_for(widest);
+  if (blocks > 1024) blocks = 1024;  // grid-stride: at most 4096 waves touch the four counters
+  hipLaunchKernelGGL(k_kg_stats, dim3(blocks), dim3(kBlock), 0, st, h, r, t, n, cf_u, cf_i, n_cf,
+                     reinterpret_cast<unsigned long long*>(stats));
+  hgd_status s = check_launch("hgd_kg_expand stats");
+  if (s != HGD_OK) return s;
+  hipLaunchKernelGGL(k_kg_expand, dim3(grid_for(total)), dim3(kBlock), 0, st, h, r, t, n, cf_u,
+                     cf_i, n_cf, stats, h_out, r_out, t_out, h32_out, r32_out, t32_out);
+  return check_launch("hgd_kg_expand");
 }

@@ -202,3 +202,122 @@ class InteractionGraph:
     def item(self) -> dict:
         """raw item id → dense id (Interaction.item)."""
         return {int(r): k for k, r in enumerate(self.item_raw.cpu().tolist())}
+
+
+class KgCSR:
+    """``train_kg_dict`` as a device CSR by head id: row ``h`` = ``rowptr[h] : rowptr[h+1]`` of
+    ``tail`` / ``rel`` (int32), in the order the triples appear in the table."""
+
+    def __init__(self, rowptr: torch.Tensor, tail: torch.Tensor, rel: torch.Tensor):
+        self.rowptr, self.tail, self.rel = rowptr, tail, rel
+
+
+class KnowledgeGraph:
+    """Knowledge's tables (data/knowledge.py:11-196) built on the device.
+
+    ``training`` is the ``[user, item, weight]`` record list of ``FileIO.load_data_set`` (or an
+    ``[n, >= 2]`` array); the KG is three integer arrays, or a DataFrame with columns ``h``,
+    ``r``, ``t`` passed as ``kg_h``. Ids are non-negative and below 2^31 - 2.
+
+    The triple table keeps the reference's order (``construct_data``, knowledge.py:44-72): with
+    ``n0 = max(r) + 1`` the blocks ``(h, r+2, t)``, ``(t, r+n0+2, h)``, ``(t, r+n0, h)`` (the
+    second concat appends the inverse frame without the ``+2``), ``(u, 0, i)``, ``(i, 1, u)``,
+    written by ``hgd_kg_expand``. An empty KG (where the reference's ``max`` raises) is taken as
+    ``n0 = 0``: the two CF blocks alone.
+
+    Attributes: ``n_kg_train``, ``n_entities``, ``n_users_entities``, ``n_relations`` (the three
+    counts are the only device values the build reads back, with the id check next to them);
+    ``h_list`` / ``t_list`` / ``r_list`` (int64 device); ``relations`` (int64 device: the
+    relation ids in first-appearance order, the keys of ``laplacian_dict`` — its matrices are not
+    built); ``train_kg`` (:class:`KgCSR`); ``norm_kg_adj`` / ``kg_interaction_mat``
+    (:class:`Incidence`, [N, N] with N = ``n_users_entities``: the table's (h, t) pairs with
+    duplicates summed — blocks 2 and 3 repeat every pair — and its D^-1/2 A D^-1/2);
+    ``interaction`` (the :class:`InteractionGraph` of ``training``, built on first use);
+    ``entity_raw`` / ``entity`` (first-appearance map over the interleaved h, t sequence, built
+    on first use).
+    """
+
+    def __init__(self, training, kg_h, kg_r=None, kg_t=None, device=None):
+        lib = nat.load()
+        dev = torch.device(device) if device is not None else torch.device("cuda")
+        if kg_r is None and kg_t is None and hasattr(kg_h, "columns"):
+            kg_h, kg_r, kg_t = kg_h["h"], kg_h["r"], kg_h["t"]
+        cf = np.asarray(training, dtype=np.float64)
+        cf = cf.reshape(-1, 3)[:, :2] if cf.size == 0 else cf[:, :2]
+        self._cf = np.ascontiguousarray(cf.T.astype(np.int64))
+        h, r, t = (torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.int64))).to(dev)
+                   for x in (kg_h, kg_r, kg_t))
+        u, i = (torch.from_numpy(x).to(dev) for x in self._cf)
+        n, n_cf = int(h.numel()), int(u.numel())
+        if r.numel() != n or t.numel() != n:
+            raise ValueError("KnowledgeGraph: h, r and t differ in length")
+        self.device = dev
+        self.n_cf_train = n_cf
+        self.n_kg_train = total = 3 * n + 2 * n_cf
+        m = max(total, 1)
+        self.h_list, self.r_list, self.t_list = (torch.empty(m, dtype=torch.int64, device=dev)[:total]
+                                                 for _ in range(3))
+        h32, r32, t32 = (torch.empty(m, dtype=torch.int32, device=dev)[:total] for _ in range(3))
+        stats = torch.empty(4, dtype=torch.int64, device=dev)
+        st = _stream(dev)
+        nat.check(lib.hgd_kg_expand(
+            h.data_ptr() if n else None, r.data_ptr() if n else None, t.data_ptr() if n else None,
+            n, u.data_ptr() if n_cf else None, i.data_ptr() if n_cf else None, n_cf,
+            self.h_list.data_ptr(), self.r_list.data_ptr(), self.t_list.data_ptr(),
+            h32.data_ptr(), r32.data_ptr(), t32.data_ptr(), stats.data_ptr(), st),
+            "hgd_kg_expand")
+        n_ent, n_all, n0, bad = stats.cpu().tolist()
+        if bad:
+            raise ValueError(f"KnowledgeGraph: {bad} triples or records hold a negative id or "
+                             "one too large for int32 indices")
+        self.n_entities, self.n_users_entities = int(n_ent), int(n_all)
+        # max over r+2 | r+n0+2 | r+n0 | 0 | 1
+        self.n_relations = 2 * int(n0) + 2 if n else (2 if n_cf else 0)
+        self.relations = remap_first_appearance(self.r_list)[1]
+        # train_kg_dict: one stable sort by head keeps each head's triples in table order
+        N = max(self.n_users_entities, 1)
+        rowptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        tail = torch.empty(m, dtype=torch.int32, device=dev)[:total]
+        rel = torch.empty(m, dtype=torch.int32, device=dev)[:total]
+        if total:
+            keys = torch.empty(total, dtype=torch.int32, device=dev)
+            perm = torch.empty(total, dtype=torch.int32, device=dev)
+            ws = _ws(lib.hgd_sort_perm_workspace_size(total), dev)
+            nat.check(lib.hgd_sort_perm(h32.data_ptr(), total, N, keys.data_ptr(),
+                                        perm.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                      "hgd_sort_perm(heads)")
+            nat.check(lib.hgd_rowptr_from_sorted(keys.data_ptr(), total, N, rowptr.data_ptr(),
+                                                 st), "hgd_rowptr_from_sorted(heads)")
+            nat.check(lib.hgd_gather32(t32.data_ptr(), perm.data_ptr(), total, tail.data_ptr(),
+                                       st), "hgd_gather32(tails)")
+            nat.check(lib.hgd_gather32(r32.data_ptr(), perm.data_ptr(), total, rel.data_ptr(),
+                                       st), "hgd_gather32(relations)")
+        self.train_kg = KgCSR(rowptr, tail, rel)
+        # kg_interaction_mat (knowledge.py:135-148) and Graph.normalize_graph_mat's square branch
+        rp, c, v = coalesce(h32, t32, N, N)
+        self.kg_interaction_mat = _incidence(rp, c, v, N, N)
+        self.norm_kg_adj = _incidence(rp, c, normalize_graph_mat(rp, c, v, (N, N)), N, N)
+        self._interaction = None
+        self._entity = None
+
+    @property
+    def interaction(self) -> InteractionGraph:
+        if self._interaction is None:
+            self._interaction = InteractionGraph(self._cf[0], self._cf[1], self.device)
+        return self._interaction
+
+    @property
+    def entity_raw(self) -> torch.Tensor:
+        """Raw id of every entity id (``id2ent``), int64 device."""
+        if self._entity is None:
+            seq = torch.stack([self.h_list, self.t_list], dim=1).reshape(-1)
+            self._entity = remap_first_appearance(seq)[1]
+        return self._entity
+
+    @property
+    def entity(self) -> dict:
+        """raw id → entity id (Knowledge.entity)."""
+        return {int(r): k for k, r in enumerate(self.entity_raw.cpu().tolist())}
+
+    sparse_tensor = InteractionGraph.sparse_tensor
+    to_scipy = InteractionGraph.to_scipy

@@ -33,6 +33,8 @@
  *   hgd_kg_loss_forward      calculate_kg_loss, KHGRec.py:347-365 (trans_M[r], three torch.bmm,
  *                            logsigmoid, l2_reg_loss; also HD.py:371, HD2.py:368)
  *   hgd_kg_loss_backward     its autograd backward (the [B, d, dr] gradient and its index_put)
+ *   hgd_kg_expand            Knowledge.construct_data's triple table, data/knowledge.py:44-72
+ *   hgd_sample_unified       next_batch_unified, util/sampler.py:7-90 (host)
  *
  * Conventions:
  *   - All pointers are DEVICE pointers unless a parameter says "host".
@@ -729,6 +731,18 @@ hgd_status hgd_normalize_values(const int64_t* rowptr, const int32_t* col, const
                                 int64_t n_rows, const float* row_scale, const float* col_scale,
                                 float* out, void* stream);
 
+/* Device: Knowledge.construct_data's triple table (data/knowledge.py:44-72) from the raw KG
+ * (h, r, t) [n] and the CF pairs (cf_u, cf_i) [n_cf], int64. With n0 = max(r) + 1 (0 for an
+ * empty KG) the 3n + 2·n_cf output rows are, in the reference's order:
+ *   (h, r+2, t) | (t, r+n0+2, h) | (t, r+n0, h) | (cf_u, 0, cf_i) | (cf_i, 1, cf_u)
+ * written as int64 (h_out, r_out, t_out) and as int32 copies for the sorts. stats (device
+ * int64[4]) = { max(h,t)+1, max(h,t,cf_u,cf_i)+1, n0, #inputs that are negative or too large
+ * for the int32 copies }: the copies are valid only when stats[3] == 0. */
+hgd_status hgd_kg_expand(const int64_t* h, const int64_t* r, const int64_t* t, int64_t n,
+                         const int64_t* cf_u, const int64_t* cf_i, int64_t n_cf, int64_t* h_out,
+                         int64_t* r_out, int64_t* t_out, int32_t* h32_out, int32_t* r32_out,
+                         int32_t* t32_out, int64_t* stats, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Structure primitives (all deterministic; indices bit-exact with the CPU restatement).
  * ---------------------------------------------------------------------------------------- */
@@ -867,6 +881,63 @@ hgd_status hgd_sample_pairwise(uint32_t* mt_state, const int64_t* order, int64_t
                                const int64_t* user_rowptr, const int32_t* user_items,
                                int64_t n_users, int64_t n_items, int32_t n_negs, int32_t* out_u,
                                int32_t* out_i, int32_t* out_j);
+
+/* ------------------------------------------------------------------------------------------
+ * Unified CF + KG training sampler (HOST functions, host pointers): next_batch_unified
+ * (util/sampler.py:7-90), consuming Python's random stream and NumPy's legacy global
+ * RandomState bit for bit. Both states are the 625 words (624 MT19937 words + position) that
+ * random.getstate()[1] and np.random.get_state()[1:3] expose, advanced in place.
+ *   hgd_py_shuffle_rows: random.shuffle(x) on a 2-D NumPy array. Its rows are views, so the swap
+ *                        `x[i], x[j] = x[j], x[i]` degenerates to x[i] = x[j]: order[i] =
+ *                        order[j], a resample with repeated rows. order NULL: only the n - 1
+ *                        draws are consumed (the reference's shuffle(kg_data)).
+ *   hgd_sample_unified:  one batch. (1) The CF part exactly as hgd_sample_pairwise over records
+ *                        order[begin..end), int64 outputs. (2) batch_kg positions
+ *                        np.random.randint(n_sel): masked rejection on 32-bit outputs of np_state
+ *                        (none when n_sel == 1); position v yields head sel_head[v] (the head's
+ *                        position in the epoch's head order, or head_ids[that] when head_ids is
+ *                        given), sel_rel[v], sel_tail[v]. (3) per drawn triple, in order,
+ *                        all_tails[_randbelow(n_tails)] from py_state, redrawn while in the
+ *                        head's tails tail_sorted[tail_rowptr[p] : tail_rowptr[p+1]] (ascending,
+ *                        distinct). n_sel == 0 is an error (NumPy raises); a head holding every
+ *                        tail fails instead of looping forever like the reference.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct hgd_unified_batch {
+  uint32_t* py_state;
+  uint32_t* np_state;
+  /* CF part: as hgd_sample_pairwise */
+  const int64_t* order;
+  int64_t begin, end;
+  const int32_t* rec_user;
+  const int32_t* rec_item;
+  const int64_t* user_rowptr;
+  const int32_t* user_items;
+  int64_t n_users, n_items;
+  int32_t n_negs;
+  int32_t reserved;
+  /* KG part: the epoch's tables */
+  const int64_t* sel_head; /* [n_sel] head position in [0, n_heads) */
+  const int64_t* sel_rel;  /* [n_sel] */
+  const int64_t* sel_tail; /* [n_sel] */
+  int64_t n_sel;
+  const int64_t* head_ids; /* [n_heads] entity id of a position, or NULL */
+  const int64_t* all_tails; /* [n_tails] */
+  int64_t n_tails;
+  const int64_t* tail_rowptr; /* [n_heads + 1] */
+  const int64_t* tail_sorted;
+  int64_t n_heads;
+  int64_t batch_kg;
+  /* outputs: [end - begin], [end - begin], [(end - begin) * n_negs], then 4 × [batch_kg] */
+  int64_t* out_u;
+  int64_t* out_i;
+  int64_t* out_j;
+  int64_t* out_h;
+  int64_t* out_r;
+  int64_t* out_t;
+  int64_t* out_n;
+} hgd_unified_batch;
+hgd_status hgd_py_shuffle_rows(uint32_t* mt_state, int64_t* order, int64_t n);
+hgd_status hgd_sample_unified(const hgd_unified_batch* batch);
 
 /* SpAdjDropEdge's CPU keep-mask (HCCF.py:223: floor(torch.rand(nnz) + keepRate).bool()) from
  * torch's default CPU generator, bit for bit, in one host pass (HOST function). torch_state =
