@@ -284,6 +284,12 @@ _SIGNATURES = {
     "hgd_spmm_blocked_ordered": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                                          c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32,
                                          c_f32, c_i32, c_void_p]),
+    "hgd_spmm_blocked_split_workspace_size": (c_size, [ctypes.POINTER(SplitPlan), c_i32, c_i32]),
+    "hgd_spmm_blocked_split": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64,
+                                       c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32,
+                                       c_i32, c_f32, c_i32, ctypes.POINTER(SplitPlan), c_void_p,
+                                       c_size, c_void_p]),
+    "hgd_spmm_blocks_split_for": (c_i32, [c_i64, c_i32, c_i64, c_i64, c_i32]),
     "hgd_spmm_masked": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_void_p, c_i64,
                                 c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32,
                                 c_i32, c_f32, ctypes.POINTER(SplitPlan), c_void_p, c_size,

@@ -381,6 +381,63 @@ extern "C" hgd_status hgd_spmm_blocked(const int64_t* blk_start, const int32_t* 
   return hgd::spmm_launch<float, float>(r);
 }
 
+extern "C" size_t hgd_spmm_blocked_split_workspace_size(const hgd_split_plan* plans,
+                                                        int32_t n_blocks, int32_t d) {
+  if (!plans || n_blocks < 1 || n_blocks > 64) return 0;
+  size_t need = 0;  // the blocks run in stream order: the largest block's partials
+  for (int32_t k = 0; k < n_blocks; ++k) {
+    const size_t nk = hgd_spmm_workspace_size(plans + k, d);
+    need = nk > need ? nk : need;
+  }
+  return need;
+}
+
+extern "C" hgd_status hgd_spmm_blocked_split(const int64_t* blk_start, const int32_t* blk_col,
+                                             const float* blk_val, const float* row_scale,
+                                             int64_t n_rows, int64_t n_src_rows,
+                                             int64_t row_begin, int64_t row_end, const float* X,
+                                             int64_t ldx, float* Y, int64_t ldy, int32_t d,
+                                             int32_t epilogue, float slope, int32_t n_blocks,
+                                             const hgd_split_plan* plans, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  hgd::clear_error();
+  // (the block count first: it says how many plans there are to read)
+  HGD_REQUIRE(plans || n_blocks < 1 || n_blocks > 64, "hgd_spmm_blocked_split: null plans");
+  hgd::SpmmRequest r{"hgd_spmm_blocked_split", nullptr, blk_col, blk_val, row_scale, n_rows,
+                     n_src_rows, row_begin, row_end, X, ldx, Y, ldy, d, epilogue, slope};
+  r.blocked = true;
+  r.blk_start = blk_start;
+  r.n_blk = n_blocks;
+  r.blk_plans = plans;
+  r.workspace = workspace;
+  r.workspace_bytes = workspace_bytes;
+  r.stream = stream;
+  return hgd::spmm_launch<float, float>(r);
+}
+
+extern "C" int32_t hgd_spmm_blocks_split_for(int64_t n_src_rows, int32_t d, int64_t nnz,
+                                             int64_t n_chunks, int32_t chunk) {
+  if (n_src_rows <= 0 || d <= 0 || nnz <= 0 || n_chunks <= 0 || chunk <= 0) return 0;
+  // Measured on MI355X over the hop into items at 10 M users × 1 M items × 100 M draws, split at
+  // 2048 into chunks of 512, against the plain split hop, interleaved, two repeats of five rounds
+  // (scripts/bench_mall_blocked.py --zipf, profiles/blocked_split/):
+  //   items ∝ rank^-0.8 (28.6 % of the nonzeros in split rows), d = 64: 4.10 / 4.09 ms plain,
+  //     3.995 / 3.991 at P = 4 (−2.5 %, the rounds' ranges 0.02–0.05 ms), 4.00 / 4.01 at P = 2,
+  //     4.65 at P = 8;
+  //   the same at d = 128 (a 5.12 GB table): no block count beyond the plain hop's range;
+  //   items ∝ rank^-1 (60.1 % in split rows): −0.8 / −1.3 % at d = 64 with P = 2, inside the
+  //     plain hop's range on one repeat, nothing at d = 128; P = 8 is 7–24 % slower.
+  // So the rule is on exactly where a block count won on both repeats, without a margin: four
+  // blocks for a pass's gathered table (a blocked hop runs rows wider than 128 as 128-column
+  // passes) from the 2.56 GB that won to below the 5.12 GB that did not, with at most the share
+  // of the nonzeros in split rows that won. Everything else, unmeasured shapes included, is the
+  // plain split hop; HGD_SPMM_BLOCKS_SPLIT forces a block count anywhere.
+  const double table = static_cast<double>(n_src_rows) * (d < 128 ? d : 128) * 4.0;
+  if (table < 2.56e9 || table >= 5.12e9) return 0;
+  const double share = static_cast<double>(n_chunks) * chunk / static_cast<double>(nnz);
+  return share <= 0.2862 ? 4 : 0;
+}
+
 extern "C" size_t hgd_spmm_col_blocks_ordered_workspace_size(int64_t n_rows, int32_t n_blocks) {
   if (n_rows <= 0 || n_rows >= 0x7fffffffLL || n_blocks <= 0 || n_blocks > 64) return 0;
   return hgd::block_order_ws(n_rows, n_blocks).total;

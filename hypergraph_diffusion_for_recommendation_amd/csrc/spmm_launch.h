@@ -59,6 +59,10 @@ struct SpmmRequest {
   // [n_blk·n_rows], block k's at k·n_rows, in the processing order of its blk_start
   bool ordered = false;
   const int32_t* out_row = nullptr;
+  // the blocks' own split plans (hgd_spmm_blocked_split): a host array of n_blk plans, plan k
+  // built over block k's CSR (blk_start + k·n_rows), so a row is heavy per block; workspace is
+  // then the one chunk-partial buffer the blocks reuse in stream order. plan stays NULL
+  const hgd_split_plan* blk_plans = nullptr;
 };
 
 inline hgd_status check_launch(const char* fn, const char* what) {
@@ -192,6 +196,14 @@ inline hgd_status spmm_check_args(const SpmmRequest& r) {
               r.blocked ? "blk_out_row" : "out_row");
   HGD_REQUIRE(!r.blocked || (r.n_blk >= 1 && r.n_blk <= 64), "%s: blocks must be 1..64", fn);
   HGD_REQUIRE(!r.blocked || r.blk_start || r.row_end <= r.row_begin, "%s: null blk_start", fn);
+  if (r.blocked && r.blk_plans) {
+    // a block with split rows is walked by the row kernel, one without by hgd_spmm_blocked's
+    // choice (HGD_TUNE_SPMM_BLOCKED_SEG): a plan has no say in it
+    for (int32_t k = 0; k < r.n_blk; ++k)
+      if (r.blk_plans[k].flags & HGD_PLAN_SEGMENTED)
+        return fail(HGD_ERR_UNSUPPORTED, "%s: plan %d is HGD_PLAN_SEGMENTED: no segmented plan "
+                    "with source blocks", fn, k);
+  }
   HGD_REQUIRE(r.keep > 0.f, "%s: keep must be > 0 (got %g)", fn, (double)r.keep);  // (unmasked: 1)
   HGD_REQUIRE(!r.masked || r.mask || empty, "%s: null mask", fn);
   HGD_REQUIRE(d > 0, "%s: d must be > 0 (got %d)", fn, d);
@@ -287,6 +299,23 @@ hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const SpmmRequest& r) {
   } else if (plan && (plan->flags & HGD_PLAN_SEGMENTED) && !r.mask) {
     a.seg = 1;  // only without split rows: the segmented walk covers every nonzero of its rows
   }
+  if (r.blocked && r.blk_plans) {
+    // the blocks' own plans: each checked as the one above; the blocks run in stream order, so
+    // the largest one's partials are the workspace (spmm_passes sets a block's plan fields)
+    size_t need = 0;
+    for (int32_t k = 0; k < r.n_blk; ++k) {
+      const hgd_split_plan* bp = r.blk_plans + k;
+      if (!has_split_rows(bp)) continue;
+      HGD_REQUIRE(bp->chunk > 0 && bp->heavy_rows && bp->heavy_cptr && bp->chunk_heavy,
+                  "%s: incomplete split plan of block %d", r.fn, k);
+      const size_t nk = hgd_spmm_workspace_size(bp, r.d);
+      need = nk > need ? nk : need;
+    }
+    if (r.workspace_bytes < need || (need && !r.workspace))
+      return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", r.fn, r.workspace_bytes,
+                  need);
+    a.partial = static_cast<float*>(r.workspace);
+  }
   if constexpr (sizeof(TY) == 2) {
     if (r.blocked) {  // (a blocked hop has no plan: the workspace is its partials')
       const size_t need = blocked_part_bytes(r.n_rows, r.d, sizeof(TY), r.n_blk);
@@ -342,7 +371,11 @@ inline hgd_status spmm_pass_plan(const SpmmRequest& r, size_t sx, size_t sy, Spm
   int G = lanes >= 64 ? 64 : next_pow2(lanes);
   int pass_cols = spmm_tuning().pass_cols;  // HGD_TUNE_SPMM_PASS_COLS overrides every default
   if (pass_cols == 0) {
-    if (r.blocked) {
+    if (r.blocked && r.blk_plans && r.n_blk == 1) {
+      // one block with its plan is hgd_spmm with that plan, bit for bit: the fix-up's combine
+      // order is fixed by the lanes per row, so it takes hgd_spmm's passes (below)
+      pass_cols = d <= 128 ? 256 : 64;
+    } else if (r.blocked) {
       // source-blocked: every pass runs the blocks in order, the later ones adding;
       // passes of up to 128 columns: at d = 256 the blocked hop into items takes
       // 16.99 ms in 128-column passes, 18.04 in 64-column ones and 19.54 in one 256-wide pass
@@ -393,6 +426,21 @@ hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmRequest& r, const SpmmPass
           if (r.row_scale) a.row_scale = r.row_scale + static_cast<int64_t>(k) * r.n_rows;
         } else if constexpr (kF32<TX, TY>) {
           if (VEC == 4) a.seg = spmm_tuning().blocked_seg;  // (the vector path's only)
+        }
+        if (r.blk_plans) {
+          // block k's own split plan: its chunks lead this launch's grid and its fix-up follows
+          // (launch_g), both over the one workspace; a piece of a row is written once per block,
+          // by the row kernel when it is light in this block and by the fix-up when it is heavy
+          const hgd_split_plan* bp = r.blk_plans + k;
+          const bool split = has_split_rows(bp);
+          a.heavy_threshold = split ? bp->threshold : 0;
+          a.chunk = split ? bp->chunk : 0;
+          a.n_chunks = split ? bp->n_chunks : 0;
+          a.n_heavy = split ? bp->n_heavy : 0;
+          a.chunk_heavy = split ? bp->chunk_heavy : nullptr;
+          a.heavy_rows = split ? bp->heavy_rows : nullptr;
+          a.heavy_cptr = split ? bp->heavy_cptr : nullptr;
+          if (split) a.seg = 0;  // the segmented walk covers every nonzero of its rows
         }
         a.blk_accum = k > 0;
         a.epi = k + 1 == r.n_blk ? r.epilogue : HGD_EPI_NONE;  // the activation after the last

@@ -88,6 +88,8 @@ class CSR:
         self.cols_ascending = False
         self._col_blocks: Dict[int, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
         self._blk_vals: Dict[Tuple[int, int], tuple] = {}
+        self._col_block_plans: Dict[int, tuple] = {}
+        self._blk_ws_bytes: Dict[Tuple[int, int], int] = {}
         self._col_blocks_ord: Dict[int, Tuple[torch.Tensor, ...]] = {}
         self._blk_ord_vals: Dict[Tuple[int, int], tuple] = {}
         self._row_order: Optional[Tuple[torch.Tensor, ...]] = None
@@ -192,6 +194,48 @@ class CSR:
         if val is None:
             return None
         return _gather32_cached(self._blk_vals, n_blocks, val, self.col_blocks(n_blocks)[2])
+
+    def col_block_plans(self, n_blocks: int):
+        """The split plans of the source blocks of :meth:`col_blocks`, for hgd_spmm_blocked_split:
+        a ctypes array of ``n_blocks`` ``hgd_split_plan``, plan k built over block k's own CSR
+        (``blk_start + k·n_rows``) with this structure's threshold and chunk — a row is heavy per
+        block, so one of 5,000 nonzeros over 4 blocks may be light in all of them. The ``[P, 2]``
+        (n_heavy, n_chunks) counts are read from the device once; the plans and their device
+        arrays are cached per block count like the block-major copy."""
+        got = self._col_block_plans.get(n_blocks)
+        if got is None:
+            start = self.col_blocks(n_blocks)[0]
+            plans = (nat.SplitPlan * n_blocks)()
+            arrays = []
+            dev, lib, n = self.device, nat.load(), self.n_rows
+            thr, chunk = int(self.plan.threshold), int(self.plan.chunk)
+            if self.n_heavy and n:  # (without split rows no piece of a row is heavy either)
+                st = _stream(dev)
+                counts = torch.empty((n_blocks, 2), dtype=torch.int64, device=dev)
+                for k in range(n_blocks):
+                    nat.check(lib.hgd_split_plan_count(
+                        start.data_ptr() + 8 * k * n, n, thr, chunk,
+                        counts.data_ptr() + 16 * k, st), "hgd_split_plan_count")
+                ws = _ws(lib.hgd_split_plan_workspace_size(n), dev)
+                for k, (n_heavy, n_chunks) in enumerate(counts.tolist()):
+                    if n_heavy == 0:
+                        continue
+                    heavy_rows = torch.empty(n_heavy, dtype=torch.int32, device=dev)
+                    heavy_cptr = torch.empty(n_heavy + 1, dtype=torch.int64, device=dev)
+                    chunk_heavy = torch.empty(n_chunks, dtype=torch.int32, device=dev)
+                    nat.check(lib.hgd_split_plan_build(
+                        start.data_ptr() + 8 * k * n, n, thr, chunk, heavy_rows.data_ptr(),
+                        heavy_cptr.data_ptr(), chunk_heavy.data_ptr(), n_heavy, n_chunks,
+                        ws.data_ptr(), ws.numel(), st), "hgd_split_plan_build")
+                    arrays.append((heavy_rows, heavy_cptr, chunk_heavy))
+                    p = plans[k]
+                    p.threshold, p.chunk = thr, chunk
+                    p.n_heavy, p.n_chunks = n_heavy, n_chunks
+                    p.heavy_rows = heavy_rows.data_ptr()
+                    p.heavy_cptr = heavy_cptr.data_ptr()
+                    p.chunk_heavy = chunk_heavy.data_ptr()
+            got = self._col_block_plans[n_blocks] = (plans, arrays)
+        return got[0]
 
     def col_blocks_ordered(self, n_blocks: int) -> Tuple[torch.Tensor, ...]:
         """:meth:`col_blocks` with the rows of every source block in ascending order of their
@@ -332,6 +376,39 @@ def spmm_blocks(csr: CSR, d: int, x_dtype: torch.dtype = torch.float32) -> int:
     return int(nat.load().hgd_spmm_blocks_for_dt(csr.n_cols, int(d), _HOP_DTYPES[x_dtype]))
 
 
+def spmm_blocks_split(csr: CSR, d: int, x_dtype: torch.dtype = torch.float32) -> int:
+    """How many source blocks the fp32 hop over ``csr``, a structure WITH split rows, runs in at
+    width ``d`` (0 = the plain split hop, hgd_spmm with the structure's plan).
+
+    :func:`spmm_blocks` answers 0 for every structure with split rows, i.e. for every skewed
+    catalogue; this is the question it leaves open. hgd_spmm_blocked_split runs the blocks of
+    :meth:`CSR.col_blocks` each under its own split plan (:meth:`CSR.col_block_plans`): a row
+    is heavy per block, the chunk partials of one block at a time live in one workspace, and Y
+    is written once per row and block.
+
+    Only for a structure with split rows whose rows' columns ascend, without a mask or the
+    segmented flag, gathering a float32 table (into a float32 output: spmm_csr asks for no other).
+    ``HGD_SPMM_BLOCKS_SPLIT``: ``0`` off, an integer P in 2..64 forces P blocks wherever it
+    applies, unset (or ``auto``) = the library's rule (hgd_spmm_blocks_split_for, DESIGN.md
+    §4.1). ``HGD_SPMM_BLOCKS`` has no say here, nor this variable in :func:`spmm_blocks`."""
+    if x_dtype not in _HOP_DTYPES:
+        raise TypeError(f"spmm_blocks_split: x_dtype must be float32 or bfloat16, got {x_dtype}")
+    if x_dtype != torch.float32 or not csr.n_heavy:
+        return 0
+    if not csr.cols_ascending or csr.segmented or csr.nnz == 0:
+        return 0
+    if getattr(csr, "mask", None) is not None:
+        return 0
+    env = os.environ.get("HGD_SPMM_BLOCKS_SPLIT", "")
+    if env not in ("", "auto"):
+        p = int(env)
+        if p != 0 and not 2 <= p <= 64:
+            raise ValueError(f"HGD_SPMM_BLOCKS_SPLIT must be 0 or 2..64, got {env!r}")
+        return p
+    return int(nat.load().hgd_spmm_blocks_split_for(
+        csr.n_cols, int(d), csr.nnz, int(csr.plan.n_chunks), int(csr.plan.chunk)))
+
+
 def spmm_row_order(csr: CSR, d: int) -> bool:
     """Whether the plain fp32 hop over ``csr`` at width ``d`` walks its rows in ascending order
     of their smallest column (hgd_spmm_ordered over :meth:`CSR.row_order`).
@@ -406,8 +483,9 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     With ``ex`` (an ``hgd_row_epilogue``) the call is ``hgd_spmm_fused``: ``ex.act``/``ex.slope``
     replace ``epilogue``/``slope`` and the LayerNorm / residual epilogue runs in the store.
     ``blocks``: None = :func:`spmm_blocks` decides whether the hop runs source-blocked
-    (hgd_spmm_blocked); 0 = never (e.g. into uncached exchange memory, which the blocked hop
-    would read back P−1 times)."""
+    (hgd_spmm_blocked) and, for an fp32 hop over a structure with split rows,
+    :func:`spmm_blocks_split` whether it runs as hgd_spmm_blocked_split; 0 = never (e.g. into
+    uncached exchange memory, which the blocked hop would read back P−1 times)."""
     if X.dim() != 2:
         raise ValueError(f"spmm: X must be 2-D, got {tuple(X.shape)}")
     if X.dtype not in _HOP_DTYPES:
@@ -447,10 +525,13 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     if timer is not None:
         t0 = timer.begin()
     mask = getattr(csr, "mask", None)
+    split_blocks = 0  # the blocks of a structure with split rows (hgd_spmm_blocked_split)
     if mask is not None or ex is not None or blocks == 0:
         blocks = 0
     else:
         blocks = spmm_blocks(csr, d, X.dtype)
+        if not blocks and not dt and csr.n_heavy:  # spmm_blocks' 0 is for the split rows
+            split_blocks = spmm_blocks_split(csr, d, X.dtype)
     # the arguments the entry points share, evaluated once: the structure (a masked one adds its
     # mask and keep rate), row scale and row range, the table and the output, workspace and stream.
     # (Plain locals passed positionally: packing them into tuples and unpacking those into the
@@ -508,6 +589,18 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
             start.data_ptr(), bcol.data_ptr(), nat.ptr(csr.blocked_ordered_values(blocks, val)),
             nat.ptr(csr.blocked_ordered_scale(blocks, row_scale)), out_row.data_ptr(), n, m, xp,
             ldx, yp, ldy, d, int(epilogue), float(slope), blocks, st), "hgd_spmm_blocked_ordered")
+    elif split_blocks:  # (fp32, no mask, no fused epilogue)
+        start, bcol, _ = csr.col_blocks(split_blocks)
+        plans = csr.col_block_plans(split_blocks)
+        pb = csr._blk_ws_bytes.get((split_blocks, d))
+        if pb is None:
+            pb = csr._blk_ws_bytes[(split_blocks, d)] = lib.hgd_spmm_blocked_split_workspace_size(
+                plans, split_blocks, d)
+        part = _ws(pb, X.device) if pb else None
+        nat.check(lib.hgd_spmm_blocked_split(
+            start.data_ptr(), bcol.data_ptr(), nat.ptr(csr.blocked_values(split_blocks, val)), sp,
+            n, m, rb, re_, xp, ldx, yp, ldy, d, int(epilogue), float(slope), split_blocks, plans,
+            nat.ptr(part), pb, st), "hgd_spmm_blocked_split")
     elif ex is None and blocks:
         start, bcol, _ = csr.col_blocks(blocks)
         bval = csr.blocked_values(blocks, val)
@@ -526,13 +619,16 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
         full = rb == 0 and re_ == csr.n_rows
 
         def nbytes(csr=csr, rb=rb, re_=re_, full=full, d=d, hv=val is not None,
-                   hs=row_scale is not None, blocks=blocks, xb=X.element_size(),
-                   yb=out.element_size(), ordered=ordered, blk_ordered=blk_ordered):
+                   hs=row_scale is not None, blocks=blocks or split_blocks,
+                   xb=X.element_size(), yb=out.element_size(), ordered=ordered,
+                   blk_ordered=blk_ordered, split=bool(split_blocks)):
             nnz = csr.nnz if full else int(csr.rowptr[re_].item() - csr.rowptr[rb].item())
+            # (the chunks of every split row: a row range runs those of its own rows only)
+            chunks = sum(int(p.n_chunks) for p in csr.col_block_plans(blocks)) if split else 0
             return (profiling.hop_bytes(nnz, re_ - rb, d, x_bytes=xb, y_bytes=yb),
                     profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, blocks, x_bytes=xb,
                                          y_bytes=yb, ordered=ordered,
-                                         block_ordered=blk_ordered))
+                                         block_ordered=blk_ordered, split_chunks=chunks))
 
         timer.end(t0, nbytes)
     return out

@@ -37,7 +37,7 @@ def hop_bytes(nnz: int, rows: int, d: int, weighted: bool = False, x_bytes: int 
 
 def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
                blocks: int = 0, x_bytes: int = 4, y_bytes: int = 4, ordered: bool = False,
-               block_ordered: bool = False) -> int:
+               block_ordered: bool = False, split_chunks: int = 0) -> int:
     """Bytes the hgd_spmm launch streams at minimum as implemented (int64 rowptr, weights).
     A source-blocked hop (hgd_spmm_blocked, ``blocks`` = P > 1) reads the [R × (P+1)] int64
     block starts instead of the rowptr, writes every Y row P times, reads it back P−1 times and
@@ -45,7 +45,13 @@ def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
     keeps the running partial in an fp32 scratch instead: P−1 writes and P−1 reads of 4-byte
     rows, then one store of the 2-byte Y row. An ordered hop (hgd_spmm_ordered) also reads the
     int32 output row of every row, a blocked hop over per-block row orders
-    (hgd_spmm_blocked_ordered, ``block_ordered``) the one of every row in every block."""
+    (hgd_spmm_blocked_ordered, ``block_ordered``) the one of every row in every block. A blocked
+    hop over split rows (hgd_spmm_blocked_split, ``split_chunks`` = the chunks of all its blocks'
+    plans) also writes the fp32 partial of every chunk once and reads it once in the fix-up,
+    with the chunk's int32 owner."""
+    if split_chunks:
+        return (impl_bytes(nnz, rows, d, has_val, has_scale, blocks, x_bytes, y_bytes)
+                + split_chunks * (2 * 4 * d + 4))
     if ordered:
         return impl_bytes(nnz, rows, d, has_val, has_scale, 0, x_bytes, y_bytes) + rows * 4
     if blocks > 1 and block_ordered:

@@ -19,6 +19,8 @@
  *   hgd_spmm_blocked_dt      the source-blocked hop over bfloat16 tables
  *   hgd_spmm_blocked_ordered the source-blocked hop with each block's rows walked in ascending
  *                            order of their first column (hgd_spmm_col_blocks_ordered builds it)
+ *   hgd_spmm_blocked_split   the source-blocked hop over a structure with split rows (a split
+ *                            plan per source block)
  *   hgd_sort_perm            COO→CSR / CSR→CSC ordering that cuSPARSE re-derives per call
  *                            (`adj.t()` in HGCNConv.forward, HGNN_HD4.py:459; coalesce in torch.sparse.mm)
  *   hgd_rowptr_from_sorted   row pointer of a row-sorted COO  base/torch_interface.py:8-12
@@ -382,6 +384,51 @@ hgd_status hgd_spmm_blocked_ordered(const int64_t* blk_start, const int32_t* blk
                                     int64_t n_src_rows, const float* X, int64_t ldx, float* Y,
                                     int64_t ldy, int32_t d, int32_t epilogue, float slope,
                                     int32_t n_blocks, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * hgd_spmm_blocked (fp32 in and out, a row range honoured) over a structure WITH SPLIT ROWS: the
+ * skewed catalogues hgd_spmm_blocked leaves to hgd_spmm. Replaces the same call sites as
+ * hgd_spmm_blocked (torch.sparse.mm(adj.t(), X), model/graph/HGNN_HD4.py:459-462,
+ * model/graph/HCCF.py:199) when the gathered table is too large for the Infinity Cache and some
+ * rows are long enough to be split.
+ *   blk_start / blk_col / blk_val: the block-major copy of hgd_spmm_col_blocks.
+ *   plans: a HOST array of n_blocks split plans; plan k is the plan of block k's own CSR, built
+ *     with hgd_split_plan_count / hgd_split_plan_build on blk_start + k·n_rows over n_rows rows
+ *     with the parent's threshold and chunk. A row is therefore heavy PER BLOCK: a row of 5,000
+ *     nonzeros over 4 blocks may be light in all of them. A plan with n_heavy == 0 (or
+ *     threshold <= 0) is an empty plan; HGD_PLAN_SEGMENTED in any plan is HGD_ERR_UNSUPPORTED.
+ *   workspace: hgd_spmm_blocked_split_workspace_size(plans, n_blocks, d) bytes, the maximum over
+ *     the blocks of hgd_spmm_workspace_size(plan k, d): the blocks run in stream order and reuse
+ *     it. Too small: HGD_ERR_WORKSPACE.
+ * Per column pass (at most 128 columns, as hgd_spmm_blocked) and for k = 0 … n_blocks−1: one
+ * launch for block k's chunks and its light rows, one for the fix-up of its heavy rows. Block
+ * k > 0 adds to Y, the activation runs after the last block, and Y is written exactly once per
+ * row and block, whether that block's piece of the row is heavy (the fix-up writes it) or light
+ * (the row kernel does). Every sum is in a fixed order, no atomics: two runs are bitwise equal.
+ * HGD_TUNE_SPMM_BLOCKED_SEG applies to the blocks without heavy rows only.
+ * With every plan empty the call is bitwise hgd_spmm_blocked; with n_blocks = 1 it is bitwise
+ * hgd_spmm with that plan (and runs in hgd_spmm's column passes).
+ * The call allocates nothing and does not synchronise (graph-capturable).
+ *
+ * hgd_spmm_blocks_split_for: the rule both hosts would use for such a structure (host-only):
+ * the block count for a hop gathering n_src_rows rows at width d whose plan puts
+ * n_chunks·chunk / nnz of the nonzeros in split rows; 0 = run hgd_spmm. Measured on MI355X at
+ * 10 M × 1 M × 100 M (profiles/blocked_split/): 4 for a pass's gathered table
+ * (n_src_rows × min(d, 128) × 4 bytes) from 2.56 GB to below 5.12 GB with at most 28.62 % of the
+ * nonzeros in split rows, where P = 4 beat the plain split hop by 2.5 % on both repeats; 0
+ * everywhere else (items ∝ rank^-1 and d = 128 stayed inside the rounds' range).
+ * ---------------------------------------------------------------------------------------- */
+size_t hgd_spmm_blocked_split_workspace_size(const hgd_split_plan* plans, int32_t n_blocks,
+                                             int32_t d);
+hgd_status hgd_spmm_blocked_split(const int64_t* blk_start, const int32_t* blk_col,
+                                  const float* blk_val, const float* row_scale, int64_t n_rows,
+                                  int64_t n_src_rows, int64_t row_begin, int64_t row_end,
+                                  const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d,
+                                  int32_t epilogue, float slope, int32_t n_blocks,
+                                  const hgd_split_plan* plans, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int32_t hgd_spmm_blocks_split_for(int64_t n_src_rows, int32_t d, int64_t nnz, int64_t n_chunks,
+                                  int32_t chunk);
 
 /* The same hop over the EDGE-DROPPED matrix of SpAdjDropEdge (model/graph/HCCF.py:213-226:
  * mask = floor(rand + keepRate), idxs[:, mask], vals[mask] / keepRate) without building it: the

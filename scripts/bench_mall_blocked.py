@@ -22,7 +22,14 @@ HGD_SPMM_BLOCK_ORDER) instead of, or interleaved with, hgd_spmm_blocked, and che
 outputs are bitwise equal; with `both` the default block counts are 3,4,5,6, so that a shift of
 the best P shows.
 
+--zipf A draws the items ∝ rank^-A (bench.py's Zipf workload is A = 1): the CSC then has split
+rows, the plain hop is hgd_spmm with its split plan, and the blocked variants are
+hgd_spmm_blocked_split over a split plan per source block (selected through
+HGD_SPMM_BLOCKS_SPLIT; HGD_SPMM_BLOCKS has no say on such a structure). --repeats N runs the
+interleaved rounds N times in the same process and reports each.
+
     python scripts/bench_mall_blocked.py [--dim 64 --rounds 5 --table-dtype bf16]
+    python scripts/bench_mall_blocked.py --zipf 1.0 --blocks 2,4,8 --repeats 2 [--dim 128]
     python scripts/bench_mall_blocked.py --block-order both [--dim 128 --blocks 6,8,10]
 """
 import argparse
@@ -42,6 +49,11 @@ def main():
     ap.add_argument("--edges", type=int, default=100_000_000)
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="run the interleaved rounds this many times (one result line each)")
+    ap.add_argument("--zipf", type=float, default=None,
+                    help="items drawn ∝ rank^-A instead of uniformly: a CSC with split rows, "
+                         "blocked as hgd_spmm_blocked_split (fp32 only)")
     ap.add_argument("--blocks", default=None,
                     help="block counts (default 2,4,8,10,16; 3,4,5,6 with --block-order both)")
     ap.add_argument("--block-order", choices=("off", "on", "both"), default="off",
@@ -80,7 +92,7 @@ def main():
     nat.check(nat.load().hgd_set_tuning(18, args.seg), "blocked seg")
     dev = torch.device("cuda:0")
     U, I, d = args.users, args.items, args.dim
-    idx = bench.make_graph(U, I, args.edges, 0, None, dev)
+    idx = bench.make_graph(U, I, args.edges, 0, args.zipf, dev)
     inc = Incidence.from_coo(idx, None, (U, I), device=dev, validate=False, rows_sorted=True)
     del idx
     nnz = inc.nnz
@@ -108,6 +120,10 @@ def main():
         X = X.to(x_dtype) if X._base is None else X._base.to(x_dtype)[:, :d]
     if args.block_order != "off" and (x_dtype, y_dtype) != (torch.float32, torch.float32):
         ap.error("--block-order needs an fp32 table and output")
+    split = bool(S.n_heavy)  # split rows: the blocked variants are hgd_spmm_blocked_split
+    if split and ((x_dtype, y_dtype) != (torch.float32, torch.float32)
+                  or args.block_order != "off"):
+        ap.error("a structure with split rows blocks only fp32 → fp32, without block orders")
     default_blocks = "3,4,5,6" if args.block_order == "both" else "2,4,8,10,16"
     counts = [int(p) for p in (args.blocks or default_blocks).split(",")]
     orders = {"off": ["0"], "on": ["1"], "both": ["0", "1"]}[args.block_order]
@@ -122,21 +138,45 @@ def main():
         else:
             S.col_blocks(P)
             S.blocked_values(P, w_full)
+            if split:
+                S.col_block_plans(P)
 
     def run(P, order="0"):
         # HGD_SPMM_BLOCKS=0: hgd_spmm; =P: hgd_spmm_blocked over P source ranges (spmm_blocks),
-        # with HGD_SPMM_BLOCK_ORDER=1 hgd_spmm_blocked_ordered
+        # with HGD_SPMM_BLOCK_ORDER=1 hgd_spmm_blocked_ordered. Over a structure with split rows
+        # HGD_SPMM_BLOCKS_SPLIT=0: hgd_spmm with its plan; =P: hgd_spmm_blocked_split
         os.environ["HGD_SPMM_BLOCKS"] = str(P)
+        os.environ["HGD_SPMM_BLOCKS_SPLIT"] = str(P)
         os.environ["HGD_SPMM_BLOCK_ORDER"] = order
         return spmm_csr(S, X, val=w_full, row_scale=q, out_dtype=y_dtype)
 
     ref = run(0).float()
+    for rep in range(args.repeats):
+        measure(args, run, ref, S, X, R, d, nnz, y_dtype, blocks, name, split, rep)
+
+
+def measure(args, run, ref, S, X, R, d, nnz, y_dtype, blocks, name, split, rep):
+    import torch
+
+    from hypergraph_diffusion_for_recommendation_amd import profiling
     res = {"dim": d, "hop": args.hop, "pass_cols": args.pass_cols, "policy": args.policy, "unroll": args.unroll, "seg": args.seg, "ld": args.ld, "nnz": nnz,
            "table_dtype": args.table_dtype, "out_dtype": args.out_dtype or args.table_dtype,
            "rounds": args.rounds, "block_order": args.block_order,
            "bytes_algorithmic": profiling.hop_bytes(nnz, R, d, x_bytes=X.element_size(),
                                                     y_bytes=4 if y_dtype == torch.float32 else 2),
-           "variants": {}}
+           "zipf": args.zipf, "repeat": rep, "variants": {}}
+    if split:
+        # the plain hop's plan and each block count's plans: split rows and chunks (summed over
+        # the blocks), and the share of the nonzeros the plain plan puts in split rows
+        def total(P, field):
+            return sum(int(getattr(p, field)) for p in S.col_block_plans(P))
+
+        res["split"] = {"threshold": int(S.plan.threshold), "chunk": int(S.plan.chunk),
+                        "n_heavy": int(S.plan.n_heavy), "n_chunks": int(S.plan.n_chunks),
+                        "heavy_share": round(int(S.plan.n_chunks) * int(S.plan.chunk) / nnz, 4),
+                        "blocks": {str(P): {"n_heavy": total(P, "n_heavy"),
+                                            "n_chunks": total(P, "n_chunks")}
+                                   for P, _ in blocks}}
     times = {"plain": []}
     times.update({name[v]: [] for v in blocks})
     diffs = {}
