@@ -18,7 +18,7 @@ with the reference's operator signatures:
 * :mod:`.sharded`    — user-row sharding across GPUs with an RCCL all-reduce of hyperedge sums
 """
 from . import _native
-from .incidence import CSR, Incidence, incidence_of, spmm_csr
+from .incidence import CSR, Incidence, incidence_of, spmm_csr, spmm_csr_fused_dt
 from .functional import (att_two_hop, att_two_hop_fused, contrast_loss, hgconv2, mean2hop, spmm,
                          two_hop, unique_long)
 from .kg_attention import KGAttentionPattern, kg_attention
@@ -28,6 +28,7 @@ from .cf_loss import cf_loss, cf_loss_supported
 from .ingest import InteractionGraph, KnowledgeGraph
 
 __all__ = ["InteractionGraph", "KnowledgeGraph","CSR", "Incidence", "incidence_of", "spmm_csr", "spmm", "two_hop", "hgconv2",
+           "spmm_csr_fused_dt",
            "mean2hop", "contrast_loss", "unique_long", "att_two_hop", "att_two_hop_fused",
            "KGAttentionPattern", "kg_attention", "kg_loss", "kg_loss_rows", "view_attention",
            "view_attention_stacked", "view_attention_supported", "cf_loss", "cf_loss_supported",

@@ -302,6 +302,15 @@ _SIGNATURES = {
                                c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32,
                                ctypes.POINTER(RowEpilogue), ctypes.POINTER(SplitPlan), c_void_p,
                                c_size, c_void_p]),
+    "hgd_spmm_fused_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64,
+                                  c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i64, c_i32,
+                                  ctypes.POINTER(RowEpilogue), c_void_p, c_i64,
+                                  ctypes.POINTER(SplitPlan), c_void_p, c_size, c_void_p]),
+    "hgd_spmm_masked_fused_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_void_p,
+                                         c_i64, c_i64, c_i64, c_i64, c_void_p, c_i32, c_i64,
+                                         c_void_p, c_i64, c_i32, ctypes.POINTER(RowEpilogue),
+                                         c_void_p, c_i64, ctypes.POINTER(SplitPlan), c_void_p,
+                                         c_size, c_void_p]),
     "hgd_row_epilogue_forward": (c_i32, [c_void_p, c_i64, c_i64, c_i32,
                                          ctypes.POINTER(RowEpilogue), c_void_p, c_i64,
                                          c_void_p]),

@@ -1,5 +1,6 @@
 // The SpMM hop of spmm.hip over 16-bit tables: hgd_spmm_dt / hgd_spmm_masked_dt /
-// hgd_spmm_blocked_dt.
+// hgd_spmm_blocked_dt, and the fused row epilogue over a bfloat16 table: hgd_spmm_fused_dt /
+// hgd_spmm_masked_fused_dt.
 //
 // Replaces the same call sites as hgd_spmm (torch.sparse.mm(adj, X), model/graph/HCCF.py:199;
 // torch.sparse.mm(adj.t(), X), model/graph/HGNN_HD4.py:459-462, HGCN.py:173-175; paths relative
@@ -83,6 +84,83 @@ extern "C" hgd_status hgd_spmm_masked_dt(const int64_t* rowptr, const int32_t* c
   r.mask = mask;
   r.keep = keep;
   return hgd::spmm_dt_dispatch(r, x_dtype, y_dtype);
+}
+
+// The fused row epilogue (hgd_spmm_fused / hgd_spmm_masked_fused; HGCNConv + LayerNorm + residual,
+// model/layers/EquivSetConv.py:86-107, model/graph/HGNN_HD3.py:705-720; HCCF's layer,
+// model/graph/HCCF.py:182-187) over a bfloat16 table: the bf16→f32 instantiation of the EX row
+// kernel, its masked form and the EX fix-up of split rows. Y, the side tables, the LayerNorm
+// statistics and the split-row partials are fp32; y16 (or NULL) receives the row of Y rounded to
+// bf16 from the same registers, which the next layer's first hop gathers.
+namespace hgd {
+namespace {
+
+hgd_status spmm_fused_dt(SpmmRequest r, const hgd_row_epilogue* epi, void* y16, int64_t ld_y16) {
+  HGD_REQUIRE(epi != nullptr, "%s: null epilogue descriptor", r.fn);
+  r.epilogue = epi->act;
+  r.slope = epi->slope;
+  r.ex = epi;
+  r.y16 = y16;
+  r.ld_y16 = ld_y16;
+  return spmm_launch<bf16, float>(r);
+}
+
+}  // namespace
+}  // namespace hgd
+
+extern "C" hgd_status hgd_spmm_fused_dt(const int64_t* rowptr, const int32_t* col,
+                                        const float* val, const float* row_scale, int64_t n_rows,
+                                        int64_t n_src_rows, int64_t row_begin, int64_t row_end,
+                                        const void* X, int32_t x_dtype, int64_t ldx, float* Y,
+                                        int64_t ldy, int32_t d, const hgd_row_epilogue* epi,
+                                        void* y16, int64_t ld_y16, const hgd_split_plan* plan,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(hgd::dtype_ok(x_dtype),
+              "hgd_spmm_fused_dt: unknown dtype code (x %d): HGD_DT_F32 or HGD_DT_BF16", x_dtype);
+  if (x_dtype == HGD_DT_F32) {
+    if (y16)
+      return hgd::fail(HGD_ERR_UNSUPPORTED,
+                       "hgd_spmm_fused_dt: y16 needs a bfloat16 table (x HGD_DT_F32)");
+    return hgd_spmm_fused(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end,
+                          static_cast<const float*>(X), ldx, Y, ldy, d, epi, plan, workspace,
+                          workspace_bytes, stream);
+  }
+  hgd::SpmmRequest r{"hgd_spmm_fused_dt", rowptr, col, val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, HGD_EPI_NONE, 0.f, plan, workspace,
+                     workspace_bytes, stream};
+  return hgd::spmm_fused_dt(r, epi, y16, ld_y16);
+}
+
+extern "C" hgd_status hgd_spmm_masked_fused_dt(const int64_t* rowptr, const int32_t* col,
+                                               const float* val, const uint8_t* mask, float keep,
+                                               const float* row_scale, int64_t n_rows,
+                                               int64_t n_src_rows, int64_t row_begin,
+                                               int64_t row_end, const void* X, int32_t x_dtype,
+                                               int64_t ldx, float* Y, int64_t ldy, int32_t d,
+                                               const hgd_row_epilogue* epi, void* y16,
+                                               int64_t ld_y16, const hgd_split_plan* plan,
+                                               void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(hgd::dtype_ok(x_dtype),
+              "hgd_spmm_masked_fused_dt: unknown dtype code (x %d): HGD_DT_F32 or HGD_DT_BF16",
+              x_dtype);
+  if (x_dtype == HGD_DT_F32) {
+    if (y16)
+      return hgd::fail(HGD_ERR_UNSUPPORTED,
+                       "hgd_spmm_masked_fused_dt: y16 needs a bfloat16 table (x HGD_DT_F32)");
+    return hgd_spmm_masked_fused(rowptr, col, val, mask, keep, row_scale, n_rows, n_src_rows,
+                                 row_begin, row_end, static_cast<const float*>(X), ldx, Y, ldy, d,
+                                 epi, plan, workspace, workspace_bytes, stream);
+  }
+  hgd::SpmmRequest r{"hgd_spmm_masked_fused_dt", rowptr, col, val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, HGD_EPI_NONE, 0.f, plan, workspace,
+                     workspace_bytes, stream};
+  r.masked = true;
+  r.mask = mask;
+  r.keep = keep;
+  return hgd::spmm_fused_dt(r, epi, y16, ld_y16);
 }
 
 // The source-blocked hop (hgd_spmm_blocked) over 16-bit tables: the launcher's block loop over the

@@ -66,6 +66,11 @@ struct SpmmArgsT {
   float* blk_part;
   int64_t ld_part;
   int32_t blk_last;
+  // fused row epilogue over a 16-bit table (hgd_spmm_fused_dt; read by the EX instantiations with
+  // a 16-bit TX only): a bf16 copy [n_rows, ld_y16] of the row just written to the fp32 Y, rounded
+  // from the same registers, for the next layer's hop to gather. NULL: no copy
+  bf16* y16;
+  int64_t ld_y16;
 };
 using SpmmArgs = SpmmArgsT<>;
 
@@ -90,7 +95,8 @@ constexpr int kPolPrefetch = 8;  // software-pipelined index batches (see gather
 // Scale, epilogue and store of one finished row r (all G lanes of the group call it together);
 // yr is its row of Y (r, or the ordered hop's out_row[r]).
 // With EX the hgd_row_epilogue runs in registers: the group holds the whole row (single column
-// pass, checked on the host), so the LayerNorm statistics are two group_sum butterflies.
+// pass, checked on the host), so the LayerNorm statistics are two group_sum butterflies; over a
+// 16-bit table (hgd_spmm_fused_dt) the fp32 row that goes to Y is also stored rounded to a.y16.
 // BLK_PART: the caller can be a launch of a source-blocked hop into a 16-bit Y (the row kernel
 // without a mask only: the others are the code they were).
 template <int G, int VEC, bool EX, bool NT_STORE, class TX = float, class TY = float,
@@ -177,6 +183,9 @@ __device__ __forceinline__ void finish_row(const SpmmArgsT<TX, TY>& a, int64_t r
     }
   }
   if (col_ok) store_vec<VEC, NT_STORE>(a.Y + yr * a.ldy + coff, acc);
+  if constexpr (EX && sizeof(TX) == 2) {
+    if (a.y16 && col_ok) store_vec<VEC>(a.y16 + r * a.ld_y16 + coff, acc);
+  }
   if constexpr (EX) {
     const hgd_row_epilogue& e = a.ex;
     if (e.sum_out && col_ok) {
@@ -644,9 +653,19 @@ __global__ __launch_bounds__(kBlock) void spmm_fixup_kernel(SpmmArgsT<TX, TY> a)
   if (g != 0) return;  // group 0 (all of its lanes: finish_row reduces over the group)
 #pragma unroll
   for (int i = 0; i < VEC; ++i) acc[i] = s_acc[0][l * VEC + i];
-  for (int k = 1; k < GPB; ++k)
+  if constexpr (EX && sizeof(TX) == 2) {
+    // (the fused epilogue over a 16-bit table: the same sums in the same order, four groups at a
+    // time — unrolled in full, a narrow group's GPB·VEC loads are all hoisted: 256 VGPRs at
+    // d = 64 and private memory at d = 32)
+#pragma unroll 4
+    for (int k = 1; k < GPB; ++k)
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] += s_acc[k][l * VEC + i];
+      for (int i = 0; i < VEC; ++i) acc[i] += s_acc[k][l * VEC + i];
+  } else {
+    for (int k = 1; k < GPB; ++k)
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) acc[i] += s_acc[k][l * VEC + i];
+  }
   const float s = a.row_scale ? a.row_scale[r] : 1.f;
   finish_row<G, VEC, EX, false>(a, r, r, s, l, coff, col_ok, acc);
 }

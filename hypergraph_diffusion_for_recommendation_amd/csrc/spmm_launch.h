@@ -18,6 +18,22 @@ static_assert(SpmmTuning{}.policy == kDefaultPolicy && SpmmTuning{}.unroll == 8)
 template <class TX, class TY>
 constexpr bool kF32 = std::is_same_v<TX, float> && std::is_same_v<TY, float>;
 
+// The element types the fused row epilogue (EX) is instantiated for: f32→f32 (hgd_spmm_fused) and
+// a 16-bit table into an fp32 Y (hgd_spmm_fused_dt).
+template <class TX, class TY>
+constexpr bool kFusable = std::is_same_v<TY, float>;
+
+// The segmented walk with the fused row epilogue is fp32-only: a fused hop over a 16-bit table
+// walks a segmented plan's rows with the row kernel (the same sums, in edge order per row). One
+// rule, read at run time where the request is turned into arguments (spmm_fill_args) and at
+// compile time where the kernels are instantiated (pick_kernel, launch_g).
+template <class TX, class TY>
+constexpr bool seg_walk(bool fused) {
+  return kF32<TX, TY> || !fused;
+}
+template <bool EX, class TX, class TY>
+constexpr bool kSegWalk = seg_walk<TX, TY>(EX);
+
 // One hop as its extern "C" entry point describes it: the entry point fills a request and calls
 // spmm_launch (or spmm_dt.hip's dtype switch), and everything below reads the request. The
 // members down to stream are hgd_spmm's arguments in its order, so an entry point initialises
@@ -45,6 +61,9 @@ struct SpmmRequest {
   size_t workspace_bytes = 0;
   void* stream = nullptr;
   const hgd_row_epilogue* ex = nullptr;  // the fused row epilogue
+  // ... and, over a 16-bit table (hgd_spmm_fused_dt), the bf16 copy of the rows it writes
+  void* y16 = nullptr;
+  int64_t ld_y16 = 0;
   // the edge-dropped view (masked: the entry point takes one)
   bool masked = false;
   const uint8_t* mask = nullptr;
@@ -78,7 +97,7 @@ auto pick_kernel(const SpmmArgsT<TX, TY>& a, bool seg) {
     // masked (edge-dropped view) hop: the row kernel only
     if (a.mask) return spmm_kernel<G, VEC, U, HAS_VAL, POL, EX, true, TX, TY>;
   }
-  if constexpr (G >= 8) {
+  if constexpr (G >= 8 && kSegWalk<EX, TX, TY>) {
     if (seg) return spmm_seg_kernel<G, VEC, U, HAS_VAL, POL, EX, TX, TY>;
   }
   if constexpr (kF32<TX, TY> && !EX) {
@@ -127,7 +146,7 @@ template <int G, int VEC, bool EX, class TX, class TY>
 hgd_status launch_g(SpmmArgsT<TX, TY> a, const SpmmRequest& r) {
   constexpr int GPB = kBlock / G;
   const int64_t rows = a.row_end - a.row_begin;
-  if constexpr (G >= 8) {
+  if constexpr (G >= 8 && kSegWalk<EX, TX, TY>) {
     if (a.seg) {
       const int64_t sblocks = (rows + static_cast<int64_t>(GPB) * G - 1) / (GPB * G);
       if (sblocks <= 0) return HGD_OK;
@@ -225,6 +244,7 @@ inline hgd_status spmm_check_args(const SpmmRequest& r) {
                 "%s: sum_out and sum_res go together", fn);
     HGD_REQUIRE(!ex->sum_out || (ex->ld_sum_out >= d && ex->ld_sum_res >= d),
                 "%s: ld_sum_out / ld_sum_res < d", fn);
+    HGD_REQUIRE(!r.y16 || r.ld_y16 >= d, "%s: ld_y16 < d", fn);
   }
   if (!empty) {
     // col / X may be NULL for a structure without nonzeros (never dereferenced then); a blocked
@@ -280,6 +300,8 @@ hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const SpmmRequest& r) {
   a.inv_keep = pow2 ? 1.f / r.keep : 0.f;
   a.mask_pair = t.mask_pair;
   a.out_row = r.out_row;
+  a.y16 = static_cast<bf16*>(r.y16);
+  a.ld_y16 = r.ld_y16;
   const hgd_split_plan* plan = r.plan;
   if (has_split_rows(plan)) {
     HGD_REQUIRE(plan->chunk > 0 && plan->heavy_rows && plan->heavy_cptr && plan->chunk_heavy,
@@ -296,7 +318,8 @@ hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const SpmmRequest& r) {
     a.heavy_rows = plan->heavy_rows;
     a.heavy_cptr = plan->heavy_cptr;
     a.partial = static_cast<float*>(r.workspace);
-  } else if (plan && (plan->flags & HGD_PLAN_SEGMENTED) && !r.mask) {
+  } else if (plan && (plan->flags & HGD_PLAN_SEGMENTED) && !r.mask &&
+             seg_walk<TX, TY>(r.ex != nullptr)) {
     a.seg = 1;  // only without split rows: the segmented walk covers every nonzero of its rows
   }
   if (r.blocked && r.blk_plans) {
@@ -354,7 +377,7 @@ inline hgd_status spmm_pass_plan(const SpmmRequest& r, size_t sx, size_t sy, Spm
   if (ex)
     aligned = aligned && al16(ex->res1, ex->ld_res1, 4) && al16(ex->res2, ex->ld_res2, 4) &&
               al16(ex->act_out, ex->ld_act, 4) && al16(ex->sum_out, ex->ld_sum_out, 4) &&
-              al16(ex->sum_res, ex->ld_sum_res, 4);
+              al16(ex->sum_res, ex->ld_sum_res, 4) && al16(r.y16, r.ld_y16, 2);
   if (ex && ex->layer_norm && (aligned ? d > 256 : d > 64))
     return fail(HGD_ERR_UNSUPPORTED,
                 "%s: layer_norm needs d <= 256 (16-byte aligned rows) or d <= 64 (got d=%d%s)",
@@ -393,13 +416,16 @@ inline hgd_status spmm_pass_plan(const SpmmRequest& r, size_t sx, size_t sy, Spm
     }
   }
   if (!ex && vec * G > pass_cols) G = pass_cols / vec;
+  // (a fused row wider than 256 columns, which has no LayerNorm: 256-column passes of 32 lanes)
+  if (ex && !f32 && G > 32) G = 32;
   p->G = G;
   p->step = vec * G;
   return HGD_OK;
 }
 
-// The column passes of one hop over VEC-column lanes. The fused epilogue and the interleaved single
-// launch are fp32-only, as is the segmented walk of a source block's rows:
+// The column passes of one hop over VEC-column lanes. The fused epilogue needs an fp32 Y (over a
+// 16-bit table: hgd_spmm_fused_dt) and the interleaved single launch is fp32-only, as is the
+// segmented walk of a source block's rows:
 // HGD_TUNE_SPMM_PASS_INTERLEAVE and HGD_TUNE_SPMM_BLOCKED_SEG have no effect on a 16-bit hop.
 template <int VEC, class TX, class TY>
 hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmRequest& r, const SpmmPassPlan& p) {
@@ -446,7 +472,7 @@ hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmRequest& r, const SpmmPass
         a.epi = k + 1 == r.n_blk ? r.epilogue : HGD_EPI_NONE;  // the activation after the last
         a.blk_last = k + 1 == r.n_blk;  // (read for a 16-bit Y only: it then leaves the scratch)
       }
-      if constexpr (kF32<TX, TY>) {
+      if constexpr (kFusable<TX, TY>) {
         s = fused ? launch_vec<VEC, true>(p.G, a, r) : launch_vec<VEC, false>(p.G, a, r);
       } else {
         s = launch_vec<VEC, false>(p.G, a, r);

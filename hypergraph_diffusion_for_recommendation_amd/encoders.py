@@ -328,10 +328,16 @@ def _self_attend(block, x):
     return block(x.unsqueeze(1)).squeeze(1)
 
 
-def _hgcn_ln_res_stack(inc, x, lns, slope, res, attend=None):
+def _hgcn_ln_res_stack(inc, x, lns, slope, res, attend=None, gather_dtype=None):
     """``lns[k](HGCNConv(A, x)) + res`` per layer, no activation on the last (HGNN_cp.py:403-406,
     :428-433): one fused two-hop per layer whose store applies the LeakyReLU, the LayerNorm
-    and the residual; ``attend[k]`` (the UGformer blocks) first when given."""
+    and the residual; ``attend[k]`` (the UGformer blocks) first when given.
+
+    ``gather_dtype`` (the module's attribute; None or torch.bfloat16): the hops gather bfloat16
+    tables (functional.two_hop_fused). Every layer but the last then also returns the bf16 copy
+    of its output, which the next layer gathers instead of casting its input — except after a
+    UGformer block, whose output has no copy. Parameters, residuals, outputs and gradients stay
+    float32."""
     L = len(lns)
     # every layer reads res (and layer 0 reads x, the same table at the call sites): one n-ary
     # gradient pass instead of a chain of full-table accumulations (functional.fan)
@@ -340,11 +346,20 @@ def _hgcn_ln_res_stack(inc, x, lns, slope, res, attend=None):
         x, ress = uses[0], uses[1:]
     else:
         ress = fan(res, L)
+    x16 = None
     for k in range(L):
         if attend is not None:
-            x = _self_attend(attend[k], x)
-        x = two_hop_fused(inc, x, epilogue=None if k == L - 1 else "leaky_relu", slope=slope,
-                          norm=lns[k], res1=ress[k], res1_scale=1.0)
+            x, x16 = _self_attend(attend[k], x), None
+        if gather_dtype is None:
+            x = two_hop_fused(inc, x, epilogue=None if k == L - 1 else "leaky_relu", slope=slope,
+                              norm=lns[k], res1=ress[k], res1_scale=1.0)
+        elif k == L - 1:
+            x = two_hop_fused(inc, x, epilogue=None, slope=slope, norm=lns[k], res1=ress[k],
+                              res1_scale=1.0, gather_dtype=gather_dtype, x16=x16)
+        else:
+            x, x16 = two_hop_fused(inc, x, epilogue="leaky_relu", slope=slope, norm=lns[k],
+                                   res1=ress[k], res1_scale=1.0, gather_dtype=gather_dtype,
+                                   x16=x16, return_x16=True)
     return x
 
 
@@ -370,6 +385,9 @@ class SelfAwareEncoder(nn.Module):
         self.dropout = nn.Dropout(drop_rate)
         self.edgeDropper = SpAdjDropEdge()
         self.use_self_att = use_self_att
+        # None, or torch.bfloat16: the layers' hops gather bfloat16 tables (_hgcn_ln_res_stack);
+        # set after construction, so the reference's constructor signature stays
+        self.gather_dtype = None
         self.hgnn_layers = nn.ModuleList()
         self.ugformer_layers = nn.ModuleList()
         self.lns = nn.ModuleList()
@@ -383,7 +401,8 @@ class SelfAwareEncoder(nn.Module):
         inc = incidence_of(sparse_norm_adj)
         attend = self.ugformer_layers if self.use_self_att else None
         ego_embeddings = _hgcn_ln_res_stack(inc, ego_embeddings, list(self.lns), self.leaky,
-                                            ego_embeddings, attend)
+                                            ego_embeddings, attend,
+                                            getattr(self, "gather_dtype", None))
         nu = self.data.n_users
         return split_rows(ego_embeddings, nu)
 
@@ -399,6 +418,7 @@ class RelationalAwareEncoder(nn.Module):
         self.leaky = leaky
         self.dropout = dropout
         self.n_layers = n_layers
+        self.gather_dtype = None  # or torch.bfloat16, set after construction (SelfAwareEncoder)
         self.act = nn.LeakyReLU(self.leaky)
         self.convs = nn.ModuleList()
         self.lns = nn.ModuleList()
@@ -408,7 +428,8 @@ class RelationalAwareEncoder(nn.Module):
 
     def forward(self, embs, sparse_adj, att_adj=None):
         return _hgcn_ln_res_stack(incidence_of(sparse_adj), embs, list(self.lns),
-                                  float(self.leaky), embs)
+                                  float(self.leaky), embs,
+                                  gather_dtype=getattr(self, "gather_dtype", None))
 
 
 class KHGRecRelationalAwareEncoder(nn.Module):
@@ -425,6 +446,7 @@ class KHGRecRelationalAwareEncoder(nn.Module):
         self.leaky = leaky
         self.dropout = dropout
         self.n_layers = n_layers
+        self.gather_dtype = None  # or torch.bfloat16, set after construction (SelfAwareEncoder)
         self.convs = nn.ModuleList()
         self.lns = nn.ModuleList()
         for _ in range(n_layers):
@@ -437,10 +459,22 @@ class KHGRecRelationalAwareEncoder(nn.Module):
         L = self.n_layers
         uses = fan(embs, L + 1)  # one n-ary gradient sum of the residual (_hgcn_ln_res_stack)
         x, res = uses[0], uses[1:]
+        gather_dtype = getattr(self, "gather_dtype", None)
+        x16 = None  # the bf16 copy of x a layer's store hands to the next (gather_dtype set)
         for k in range(L):
-            x = att_two_hop_fused(att, inc, x, epilogue=None if k == L - 1 else "leaky_relu",
-                                  slope=float(self.leaky), norm=self.lns[k], res1=res[k],
-                                  res1_scale=1.0)
+            if gather_dtype is None:
+                x = att_two_hop_fused(att, inc, x, epilogue=None if k == L - 1 else "leaky_relu",
+                                      slope=float(self.leaky), norm=self.lns[k], res1=res[k],
+                                      res1_scale=1.0)
+            elif k == L - 1:
+                x = att_two_hop_fused(att, inc, x, epilogue=None, slope=float(self.leaky),
+                                      norm=self.lns[k], res1=res[k], res1_scale=1.0,
+                                      gather_dtype=gather_dtype, x16=x16)
+            else:
+                x, x16 = att_two_hop_fused(att, inc, x, epilogue="leaky_relu",
+                                           slope=float(self.leaky), norm=self.lns[k],
+                                           res1=res[k], res1_scale=1.0,
+                                           gather_dtype=gather_dtype, x16=x16, return_x16=True)
         return x
 
 

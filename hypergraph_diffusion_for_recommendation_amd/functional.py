@@ -33,7 +33,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as nat
-from .incidence import Incidence, spmm_csr
+from .incidence import Incidence, spmm_csr, spmm_csr_fused_dt
 
 _EPI = {None: nat.EPI_NONE, "none": nat.EPI_NONE, "leaky_relu": nat.EPI_LEAKY_RELU,
         "relu": nat.EPI_RELU}
@@ -168,6 +168,12 @@ def mean2hop(inc: Incidence, X: torch.Tensor,
 def _ln_supported(d: int) -> bool:
     # hgd_spmm_fused / hgd_row_epilogue_backward keep a whole row in one lane group
     return d <= 256 if d % 4 == 0 else d <= 64
+
+
+def _ln_supported16(d: int) -> bool:
+    # hgd_spmm_fused_dt: over a bf16 table a lane of the 16-byte path owns 8 columns, so the row
+    # is in one lane group up to d = 256 only when d % 8 == 0; else one column per lane, d <= 64
+    return d <= 256 if d % 8 == 0 else d <= 64
 
 
 # ---- the fused row epilogue out_scale·LN(act(Z)) + s1·res1 + s2·res2: its host protocol --------
@@ -328,18 +334,95 @@ class _FusedTwoHop(torch.autograd.Function):
         return dX, dgamma, dbeta, dres1, dres2, None, None, None
 
 
+def _gather16(what: str, gather_dtype, X: torch.Tensor, x16, return_x16: bool) -> bool:
+    """Whether the operator ``what`` gathers bfloat16 tables (``gather_dtype``: None or
+    torch.bfloat16, asked for by the caller and never read off a tensor), after checking what
+    goes with it: a caller's ``x16`` is its bf16 copy of ``X``."""
+    if gather_dtype is None:
+        if x16 is not None or return_x16:
+            raise ValueError(f"{what}: x16 / return_x16 go with gather_dtype=torch.bfloat16")
+        return False
+    if gather_dtype != torch.bfloat16:
+        raise TypeError(f"{what}: gather_dtype must be None or torch.bfloat16, got "
+                        f"{gather_dtype}")
+    if x16 is not None:
+        if x16.dtype != torch.bfloat16:
+            raise TypeError(f"{what}: x16 must be bfloat16, got {x16.dtype}")
+        if x16.shape != X.shape or x16.device != X.device:
+            raise ValueError(f"{what}: x16 {tuple(x16.shape)} on {x16.device} is no copy of X "
+                             f"{tuple(X.shape)} on {X.device}")
+    return True
+
+
+class _FusedTwoHop16(torch.autograd.Function):
+    """:class:`_FusedTwoHop` gathering bfloat16 tables: X16 = bf16(X) (or the caller's copy), the
+    intermediate M stored in bf16 (as :func:`two_hop` stores it for a bf16 X), and the second
+    hop's fused store reading it (hgd_spmm_fused_dt) into a float32 Y, with the bf16 copy of Y
+    as a second, non-differentiable output on request. Backward: the epilogue's gradient in
+    fp32 as before, then dM stored in bf16 and dX in fp32."""
+
+    @staticmethod
+    def forward(ctx, X, gamma, beta, res1, res2, inc: Incidence, scales, cfg, x16,
+                return_x16: bool):
+        P, Q, R = scales
+        X16 = x16.contiguous() if x16 is not None else X.contiguous().bfloat16()
+        M16 = spmm_csr(inc.csc, X16, val=inc.edge_values("csc", R), row_scale=inc.scale("col", Q))
+        n, d = inc.n_rows, X.shape[1]
+        ex = _row_epilogue_setup(ctx, n, d, X.device, gamma, beta, res1, res2, cfg)
+        ctx.inc, ctx.scales = inc, scales
+        Y16 = torch.empty((n, d), dtype=torch.bfloat16, device=X.device) if return_x16 else None
+        Y = spmm_csr_fused_dt(inc.csr, M16, ex(), val=inc.val, row_scale=inc.scale("row", P),
+                              out16=Y16)
+        if not return_x16:
+            return Y
+        ctx.mark_non_differentiable(Y16)
+        return Y, Y16
+
+    @staticmethod
+    def backward(ctx, dY, _dY16=None):
+        inc = ctx.inc
+        P, Q, R = ctx.scales
+        need_dx = ctx.needs_input_grad[0]
+        dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
+            ctx, dY.contiguous(), need_dx)
+        dX = None
+        if need_dx:
+            q = inc.scale("col", Q)
+            if dz_scale != 1.0:  # a pure blend (see _FusedTwoHop.backward)
+                q = (torch.full((inc.n_cols,), dz_scale, dtype=torch.float32, device=dZ.device)
+                     if q is None else q * dz_scale)
+            dM16 = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q,
+                            out_dtype=torch.bfloat16)
+            dX = spmm_csr(inc.csr, dM16, val=inc.val, row_scale=inc.scale("row", R),
+                          out_dtype=torch.float32)
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None
+
+
 def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
                   Q: Optional[str] = None, R: Optional[str] = None,
                   epilogue: Optional[str] = None, slope: float = 0.0,
                   norm: Optional[torch.nn.LayerNorm] = None, out_scale: float = 1.0,
                   res1: Optional[torch.Tensor] = None, res1_scale: float = 1.0,
-                  res2: Optional[torch.Tensor] = None, res2_scale: float = 1.0) -> torch.Tensor:
+                  res2: Optional[torch.Tensor] = None, res2_scale: float = 1.0,
+                  gather_dtype: Optional[torch.dtype] = None,
+                  x16: Optional[torch.Tensor] = None, return_x16: bool = False):
     """``out_scale·norm(epi(P·A·Q·Aᵀ·R·X)) + res1_scale·res1 + res2_scale·res2`` with autograd.
 
     One fused hgd_spmm_fused store replaces the reference's separate LayerNorm, residual add and
     restart blend kernels. ``norm`` is an ``nn.LayerNorm`` over the last
     dim (its weight/bias get gradients). Shapes the fused store cannot hold (LayerNorm with
-    d > 256, or a negative slope) run the same math as separate device ops."""
+    d > 256, or a negative slope) run the same math as separate device ops.
+
+    ``gather_dtype=torch.bfloat16`` (opt-in; ``X``, the residuals, γ, β, the result and every
+    gradient stay float32): both hops gather bfloat16 tables — ``bf16(X)`` and the intermediate
+    M, whose store is the one new rounding of the forward; the backward stores dM in bfloat16.
+    The fused store over a bf16 table holds a LayerNorm row up to d = 256 when d % 8 == 0 (a
+    lane owns 8 columns) and up to d = 64 otherwise; other shapes (d = 100, say, which the fp32
+    store does hold) run the hops over ``X.bfloat16()`` and then the separate device ops.
+    ``x16`` is the caller's own ``X.bfloat16()`` (saves the cast); ``return_x16`` returns
+    ``(Y, Y16)`` with ``Y16 = bf16(Y)`` written by the same store, non-differentiable — the
+    ``x16`` of a next layer."""
+    gather16 = _gather16("two_hop_fused", gather_dtype, X, x16, return_x16)
     for t in (X, res1, res2):
         if t is not None and t.dtype != torch.float32:
             raise TypeError(f"two_hop_fused: float32 only (the fused row epilogue has no 16-bit "
@@ -347,15 +430,24 @@ def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
     gamma, beta, cfg, fusable = _row_epilogue_cfg(
         "two_hop_fused", inc.n_rows, X.shape[1], epilogue, slope, norm, out_scale, res1,
         res1_scale, res2, res2_scale)
+    if gather16:
+        if fusable and not (norm is not None and not _ln_supported16(X.shape[1])):
+            return _FusedTwoHop16.apply(X, gamma, beta, res1, res2, inc, (P, Q, R), cfg, x16,
+                                        bool(return_x16))
+        y = two_hop(inc, X.bfloat16(), P=P, Q=Q, R=R, epilogue=epilogue, slope=slope,
+                    out_dtype=torch.float32)
+        y = _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
+        return (y, y.detach().bfloat16()) if return_x16 else y
     if not fusable:
         y = two_hop(inc, X, P=P, Q=Q, R=R, epilogue=epilogue, slope=slope)
         return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
     return _FusedTwoHop.apply(X, gamma, beta, res1, res2, inc, (P, Q, R), cfg)
 
 
-def _att_hops(att: Incidence, inc: Incidence, X: torch.Tensor):
-    """``K·(Kᵀ·(attᵀ·X))``: the first three of the four hops of ``adj·(adjᵀ·X)``, adj = att·K."""
-    T = spmm_csr(att.csc, X, val=att.val_t)
+def _att_hops(att: Incidence, inc: Incidence, X: torch.Tensor, store=None):
+    """``K·(Kᵀ·(attᵀ·X))``: the first three of the four hops of ``adj·(adjᵀ·X)``, adj = att·K.
+    The three results are stored in ``store`` (None: ``X``'s dtype)."""
+    T = spmm_csr(att.csc, X, val=att.val_t, out_dtype=store)
     M = spmm_csr(inc.csc, T, val=inc.val_t)
     return spmm_csr(inc.csr, M, val=inc.val)
 
@@ -434,19 +526,93 @@ class _FusedAttTwoHop(torch.autograd.Function):
         return dX, dgamma, dbeta, dres1, dres2, None, None, None
 
 
+class _AttTwoHop16(torch.autograd.Function):
+    """:class:`_AttTwoHop` over a float32 ``X`` gathering bfloat16 tables (bf16(X), T, M and Z
+    stored in bf16; the last hop writes float32), for the rows the fused store cannot hold."""
+
+    @staticmethod
+    def forward(ctx, X, att: Incidence, inc: Incidence, epi: int, slope: float):
+        Z = _att_hops(att, inc, X.contiguous().bfloat16())
+        fuse = epi != nat.EPI_NONE and slope >= 0.0
+        Y = spmm_csr(att.csr, Z, val=att.val, epilogue=epi if fuse else 0, slope=slope,
+                     out_dtype=torch.float32)
+        ref = Y
+        if epi != nat.EPI_NONE and not fuse:
+            Y = _epilogue_apply(ref, epi, slope)
+        ctx.att, ctx.inc, ctx.epi, ctx.slope = att, inc, epi, slope
+        if epi != nat.EPI_NONE:
+            ctx.save_for_backward(ref)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        dZ = dY.contiguous()
+        if ctx.epi != nat.EPI_NONE:
+            (ref,) = ctx.saved_tensors
+            dZ = _epilogue_backward(ref, dZ, ctx.epi, ctx.slope)
+        dX = spmm_csr(ctx.att.csr, _att_hops(ctx.att, ctx.inc, dZ, store=torch.bfloat16),
+                      val=ctx.att.val, out_dtype=torch.float32)
+        return dX, None, None, None, None
+
+
+class _FusedAttTwoHop16(torch.autograd.Function):
+    """:class:`_FusedAttTwoHop` gathering bfloat16 tables: bf16(X) (or the caller's copy), T, M
+    and Z stored in bf16, and the last hop's fused store reading Z (hgd_spmm_fused_dt) into a
+    float32 Y, with its bf16 copy as a second, non-differentiable output on request. Backward:
+    the epilogue's gradient in fp32, three hops stored in bf16 and dX in fp32."""
+
+    @staticmethod
+    def forward(ctx, X, gamma, beta, res1, res2, att: Incidence, inc: Incidence, cfg, x16,
+                return_x16: bool):
+        X16 = x16.contiguous() if x16 is not None else X.contiguous().bfloat16()
+        Z16 = _att_hops(att, inc, X16)
+        n, d = att.n_rows, X.shape[1]
+        ex = _row_epilogue_setup(ctx, n, d, X.device, gamma, beta, res1, res2, cfg)
+        ctx.att, ctx.inc = att, inc
+        Y16 = torch.empty((n, d), dtype=torch.bfloat16, device=X.device) if return_x16 else None
+        Y = spmm_csr_fused_dt(att.csr, Z16, ex(), val=att.val, out16=Y16)
+        if not return_x16:
+            return Y
+        ctx.mark_non_differentiable(Y16)
+        return Y, Y16
+
+    @staticmethod
+    def backward(ctx, dY, _dY16=None):
+        att = ctx.att
+        need_dx = ctx.needs_input_grad[0]
+        dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
+            ctx, dY.contiguous(), need_dx)
+        dX = None
+        if need_dx:
+            if dz_scale != 1.0:  # a pure blend
+                dZ = dZ * dz_scale
+            dX = spmm_csr(att.csr, _att_hops(att, ctx.inc, dZ, store=torch.bfloat16),
+                          val=att.val, out_dtype=torch.float32)
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None
+
+
 def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
                       epilogue: Optional[str] = None, slope: float = 0.0,
                       norm: Optional[torch.nn.LayerNorm] = None, out_scale: float = 1.0,
                       res1: Optional[torch.Tensor] = None, res1_scale: float = 1.0,
                       res2: Optional[torch.Tensor] = None,
-                      res2_scale: float = 1.0) -> torch.Tensor:
+                      res2_scale: float = 1.0,
+                      gather_dtype: Optional[torch.dtype] = None,
+                      x16: Optional[torch.Tensor] = None, return_x16: bool = False):
     """``out_scale·norm(epi(att·K·Kᵀ·attᵀ·X)) + res1_scale·res1 + res2_scale·res2`` with
     autograd: :func:`att_two_hop` with the last hop's store running the fused row epilogue, as
     :func:`two_hop_fused` does for the bare two-hop (one layer of KHGRec's
     RelationalAwareEncoder, KHGRec.py:431-438). A row of ``att`` without entries gives z = 0,
     so LayerNorm yields β and the row is β plus the residual, as in the reference. Shapes the
     fused store cannot hold (LayerNorm with d > 256, or a negative slope) run the same math as
-    separate device ops."""
+    separate device ops.
+
+    ``gather_dtype=torch.bfloat16``, ``x16`` and ``return_x16`` as in :func:`two_hop_fused`: the
+    four hops gather bfloat16 tables (bf16(X), T, M and Z are stored in bf16; three new
+    roundings before the fused store, three in the backward chain), everything a caller sees
+    stays float32. LayerNorm rows the bf16 fused store cannot hold (d > 64 with d % 8 != 0, as
+    well as d > 256) take the four bf16 hops and then the separate device ops."""
+    gather16 = _gather16("att_two_hop_fused", gather_dtype, X, x16, return_x16)
     _check_att(att, inc, X, "att_two_hop_fused")
     for t in (res1, res2):
         if t is not None and t.dtype != torch.float32:
@@ -454,6 +620,13 @@ def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
     gamma, beta, cfg, fusable = _row_epilogue_cfg(
         "att_two_hop_fused", att.n_rows, X.shape[1], epilogue, slope, norm, out_scale, res1,
         res1_scale, res2, res2_scale)
+    if gather16:
+        if fusable and not (norm is not None and not _ln_supported16(X.shape[1])):
+            return _FusedAttTwoHop16.apply(X, gamma, beta, res1, res2, att, inc, cfg, x16,
+                                           bool(return_x16))
+        y = _AttTwoHop16.apply(X, att, inc, _EPI[epilogue], float(slope))
+        y = _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
+        return (y, y.detach().bfloat16()) if return_x16 else y
     if not fusable:
         y = att_two_hop(att, inc, X, epilogue=epilogue, slope=slope)
         return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)

@@ -477,8 +477,9 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     ``out_dtype``, else ``X.dtype``. Float32 in and out is hgd_spmm (and its masked / blocked /
     fused forms); a bfloat16 side is hgd_spmm_dt / hgd_spmm_masked_dt: the same fp32 sums over
     exactly widened elements, a bf16 result rounded to nearest even on the store. A bf16 hop has
-    no fused row epilogue (``ex``); source-blocked it is hgd_spmm_blocked_dt, whose bf16 result is
-    still the fp32 result rounded once (the blocks' partials stay fp32, in a scratch).
+    no fused row epilogue (``ex``) here: that is :func:`spmm_csr_fused_dt`, asked for by name.
+    Source-blocked it is hgd_spmm_blocked_dt, whose bf16 result is still the fp32 result rounded
+    once (the blocks' partials stay fp32, in a scratch).
 
     With ``ex`` (an ``hgd_row_epilogue``) the call is ``hgd_spmm_fused``: ``ex.act``/``ex.slope``
     replace ``epilogue``/``slope`` and the LayerNorm / residual epilogue runs in the store.
@@ -629,6 +630,91 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
                     profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, blocks, x_bytes=xb,
                                          y_bytes=yb, ordered=ordered,
                                          block_ordered=blk_ordered, split_chunks=chunks))
+
+        timer.end(t0, nbytes)
+    return out
+
+
+def spmm_csr_fused_dt(csr: CSR, X16: torch.Tensor, ex: nat.RowEpilogue,
+                      val: Optional[torch.Tensor] = None,
+                      row_scale: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None,
+                      row_begin: int = 0, row_end: Optional[int] = None) -> torch.Tensor:
+    """The hop with the fused row epilogue ``ex`` gathering from the bfloat16 table ``X16``
+    (hgd_spmm_fused_dt; hgd_spmm_masked_fused_dt over an edge-dropped view): ``Y[r] =
+    ex(row_scale[r] * Σ_e val[e] * X16[col[e]])`` for r in [row_begin, row_end), a float32
+    result. Everything ``ex`` points to is float32, as for ``spmm_csr(..., ex=)``; the sums are
+    fp32 over exactly widened elements.
+
+    ``out16`` (bfloat16 [n_rows, d]) is filled with the rows of Y rounded to nearest even, from
+    the registers Y was stored from: the table a following hop gathers. Never source-blocked and
+    never walked in a row order, like the fp32 fused hop."""
+    if X16.dim() != 2:
+        raise ValueError(f"spmm_fused_dt: X16 must be 2-D, got {tuple(X16.shape)}")
+    if X16.dtype != torch.bfloat16:
+        raise TypeError(f"spmm_fused_dt: X16 must be bfloat16, got {X16.dtype}")
+    if out is not None and out.dtype != torch.float32:
+        raise TypeError(f"spmm_fused_dt: the output must be float32, got {out.dtype}")
+    if out16 is not None and out16.dtype != torch.bfloat16:
+        raise TypeError(f"spmm_fused_dt: out16 must be bfloat16, got {out16.dtype}")
+    if ex is None:
+        raise ValueError("spmm_fused_dt: needs a row epilogue (ex)")
+    if X16.device.type != "cuda":
+        raise RuntimeError("spmm_fused_dt: X16 must be a device (cuda/hip) tensor; there is no "
+                           "CPU path")
+    if X16.shape[0] != csr.n_cols:
+        raise ValueError(f"spmm_fused_dt: X16 has {X16.shape[0]} rows, structure expects "
+                         f"{csr.n_cols}")
+    if X16.stride(1) != 1:
+        X16 = X16.contiguous()
+    d = X16.shape[1]
+    if out is None:
+        out = torch.empty((csr.n_rows, d), dtype=torch.float32, device=X16.device)
+    for name, t in (("out", out), ("out16", out16)):
+        if t is not None and (tuple(t.shape) != (csr.n_rows, d) or t.stride(1) != 1
+                              or t.device != X16.device):
+            raise ValueError(f"spmm_fused_dt: {name} must be a [{csr.n_rows}, {d}] matrix with "
+                             f"unit column stride on {X16.device}")
+    if row_end is None:
+        row_end = csr.n_rows
+    if d == 0 or row_end <= row_begin:
+        return out
+    if val is not None and val.numel() != csr.nnz:
+        raise ValueError("spmm_fused_dt: val size mismatch")
+    if row_scale is not None and row_scale.numel() != csr.n_rows:
+        raise ValueError("spmm_fused_dt: row_scale size mismatch")
+    lib = nat.load()
+    plan_ptr = ctypes.byref(csr.plan)
+    wsb = csr._ws_bytes.get(d)
+    if wsb is None:
+        wsb = csr._ws_bytes[d] = lib.hgd_spmm_workspace_size(plan_ptr, d)
+    ws = _ws(wsb, X16.device) if wsb else None
+    timer = profiling.active()
+    if timer is not None:
+        t0 = timer.begin()
+    mask = getattr(csr, "mask", None)
+    rp, cp, vp = csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None, nat.ptr(val)
+    sp, n, m, rb, re_ = nat.ptr(row_scale), csr.n_rows, csr.n_cols, int(row_begin), int(row_end)
+    xp, ldx, yp, ldy = X16.data_ptr(), X16.stride(0), out.data_ptr(), out.stride(0)
+    y16p, ld16 = nat.ptr(out16), 0 if out16 is None else out16.stride(0)
+    wp, st = nat.ptr(ws), _stream(X16.device)
+    if mask is not None:
+        nat.check(lib.hgd_spmm_masked_fused_dt(
+            rp, cp, vp, mask.data_ptr() if csr.nnz else None, float(csr.keep), sp, n, m, rb, re_,
+            xp, nat.DT_BF16, ldx, yp, ldy, d, ctypes.byref(ex), y16p, ld16, plan_ptr, wp, wsb,
+            st), "hgd_spmm_masked_fused_dt")
+    else:
+        nat.check(lib.hgd_spmm_fused_dt(
+            rp, cp, vp, sp, n, m, rb, re_, xp, nat.DT_BF16, ldx, yp, ldy, d, ctypes.byref(ex),
+            y16p, ld16, plan_ptr, wp, wsb, st), "hgd_spmm_fused_dt")
+    if timer is not None:
+        full = rb == 0 and re_ == csr.n_rows
+
+        def nbytes(csr=csr, rb=rb, re_=re_, full=full, d=d, hv=val is not None,
+                   hs=row_scale is not None):
+            nnz = csr.nnz if full else int(csr.rowptr[re_].item() - csr.rowptr[rb].item())
+            return (profiling.hop_bytes(nnz, re_ - rb, d, x_bytes=2, y_bytes=4),
+                    profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, 0, x_bytes=2, y_bytes=4))
 
         timer.end(t0, nbytes)
     return out

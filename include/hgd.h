@@ -13,6 +13,8 @@
  *                            torch_scatter.scatter(.., 'mean')  model/layers/layers2/EquivSetConv2.py:88-93
  *                            (row_scale = 1/count is the scatter-mean; val = per-nonzero weight)
  *   hgd_spmm_dt              the same hops over bfloat16 tables (X and / or Y in 16 bits, fp32 sums)
+ *   hgd_spmm_fused_dt        hgd_spmm_fused (the hop with the LayerNorm / residual row epilogue in
+ *                            its store) gathering from a bfloat16 table
  *   hgd_spmm_blocked         the same torch.sparse.mm(adj.t(), X) hop for a gathered table larger
  *                            than the Infinity Cache (source-blocked; hgd_spmm_col_blocks builds
  *                            its block-major copy of the CSC)
@@ -47,8 +49,9 @@
  *   - Errors come back as hgd_status; hgd_get_last_error_string() describes the last failure
  *     on the calling thread. No C++ exception crosses the ABI.
  *   - Indices: row pointers are int64, column/row indices are int32 (rows, cols < 2^31).
- *   - Floating point is fp32 in and out (hgd_spmm_dt / hgd_spmm_masked_dt / hgd_spmm_blocked_dt also
- *     take bfloat16 tables); sums run in fp32 in edge order (deterministic).
+ *   - Floating point is fp32 in and out (hgd_spmm_dt / hgd_spmm_masked_dt / hgd_spmm_blocked_dt /
+ *     hgd_spmm_fused_dt / hgd_spmm_masked_fused_dt also take bfloat16 tables); sums run in fp32 in
+ *     edge order (deterministic).
  */
 #ifndef HGD_H
 #define HGD_H
@@ -508,6 +511,39 @@ hgd_status hgd_spmm_masked_fused(const int64_t* rowptr, const int32_t* col, cons
                                  int64_t ldy, int32_t d, const hgd_row_epilogue* epi,
                                  const hgd_split_plan* plan, void* workspace,
                                  size_t workspace_bytes, void* stream);
+
+/* hgd_spmm_fused / hgd_spmm_masked_fused gathering from a table stored in bfloat16 (x_dtype, ldx as
+ * hgd_spmm_dt). They replace the call sites those two replace (LN0(HGCNConv(adj, Xve)) + Xve,
+ * model/layers/EquivSetConv.py:86-107, model/graph/HGNN_HD3.py:705-720; the restart blend,
+ * model/layers/layers2/EquivSetConv2.py:96; HCCF's layer, model/graph/HCCF.py:182-187) when the hop
+ * input is kept or staged in 16 bits: the gathered rows are nnz·2d bytes instead of nnz·4d.
+ * Only the gathered table is 16-bit. Y is fp32, and so are the residuals, act_out, the LayerNorm
+ * statistics, γ, β, sum_res / sum_out and the split-row partials; a bf16 element is widened
+ * exactly and the sum is hgd_spmm's fp32 fmaf chain in edge order.
+ *   y16 (bf16 [n_rows, ld_y16], or NULL): a second output, the row just written to Y rounded to
+ *   nearest even from the same registers — the table the next layer's first hop gathers, without a
+ *   cast pass over Y. ld_y16 >= d; it takes part in the 16-byte test like the side tables
+ *   (ld_y16 % 8 == 0), and the 16-byte path needs d % 8 == 0.
+ *   x_dtype == HGD_DT_F32 with y16 == NULL forwards to hgd_spmm_fused / hgd_spmm_masked_fused
+ *   (bitwise theirs); HGD_DT_F32 with a y16 is HGD_ERR_UNSUPPORTED.
+ * layer_norm needs d <= 256 on the 16-byte path (a group of d/8 lanes holds the row), d <= 64
+ * otherwise. Workspace: hgd_spmm_workspace_size, unchanged. A plan with HGD_PLAN_SEGMENTED is
+ * walked by the row kernel (the same sums). */
+hgd_status hgd_spmm_fused_dt(const int64_t* rowptr, const int32_t* col, const float* val,
+                             const float* row_scale, int64_t n_rows, int64_t n_src_rows,
+                             int64_t row_begin, int64_t row_end, const void* X, int32_t x_dtype,
+                             int64_t ldx, float* Y, int64_t ldy, int32_t d,
+                             const hgd_row_epilogue* epi, void* y16, int64_t ld_y16,
+                             const hgd_split_plan* plan, void* workspace, size_t workspace_bytes,
+                             void* stream);
+hgd_status hgd_spmm_masked_fused_dt(const int64_t* rowptr, const int32_t* col, const float* val,
+                                    const uint8_t* mask, float keep, const float* row_scale,
+                                    int64_t n_rows, int64_t n_src_rows, int64_t row_begin,
+                                    int64_t row_end, const void* X, int32_t x_dtype, int64_t ldx,
+                                    float* Y, int64_t ldy, int32_t d,
+                                    const hgd_row_epilogue* epi, void* y16, int64_t ld_y16,
+                                    const hgd_split_plan* plan, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 /* The same row epilogue applied to an existing matrix Z [n_rows, ldz] (z = Z[r], no hop): the
  * LayerNorms that do not follow a hop, e.g. the MLP InputNorm of model/layers/MLP.py:65-71,109-110.

@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""Forward + backward of the KG carriers' encoders with their hops gathering fp32 tables (the
+default, ``gather_dtype=None``) and bfloat16 ones (``gather_dtype=torch.bfloat16``: every hop
+reads 2·d bytes per nonzero, the last hop of a layer runs the fused row epilogue over a bf16
+table — hgd_spmm_fused_dt — and hands the next layer the bf16 copy of its output):
+
+* self_aware d=64 / d=128 — encoders.SelfAwareEncoder (UGformer off, KHGRec's setting) at the
+  Yelp2018 shape of scripts/bench_kg_encoders.py (31,668 × 38,048, 1.24 M interactions, 3
+  layers), training mode, the edge-dropped ``norm_adj`` (keep 0.5) drawn per step on the device.
+* khgrec — encoders.KHGRecRelationalAwareEncoder at the conf/KHGRec.conf shape of
+  scripts/bench_kg_attention.py (100,000 entities, 1,000,000 KG nonzeros, B = 8192 triples,
+  d = 128, 2 layers) over one attention matrix built before the timing.
+
+All variants run interleaved in ONE call, --rounds rounds of --reps event-timed steps each; one
+JSON line per variant with the median of the rounds' medians and the rounds' range, then one line
+per encoder with the deviation of the bf16 output and gradients from the fp32 ones over the same
+structure: the largest row error relative to that row's largest fp32 magnitude, and the relative
+Frobenius distance of the whole table."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--users", type=int, default=31_668)
+    ap.add_argument("--items", type=int, default=38_048)
+    ap.add_argument("--edges", type=int, default=1_237_259)
+    ap.add_argument("--layers", type=int, default=3)
+    ap.add_argument("--entities", type=int, default=100_000)
+    ap.add_argument("--relations", type=int, default=40)
+    ap.add_argument("--kg-edges", type=int, default=1_000_000)
+    ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--kg-dim", type=int, default=128)
+    ap.add_argument("--rel-dim", type=int, default=32)
+    ap.add_argument("--kg-layers", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    import numpy as np
+    import scipy.sparse as sp
+    import torch
+
+    import refops as R
+    from hypergraph_diffusion_for_recommendation_amd.encoders import (
+        KHGRecRelationalAwareEncoder, SelfAwareEncoder, sparse_tensor_of)
+    from hypergraph_diffusion_for_recommendation_amd.kg_attention import KGAttentionPattern
+    from hypergraph_diffusion_for_recommendation_amd.layers import SpAdjDropEdge
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_fused_bf16: needs a GPU; nothing is measured without one")
+    dev = torch.device("cuda")
+    BF16 = torch.bfloat16
+    cases = {}  # name -> (step(gather_dtype, seed=None) -> [output, gradients...], shape info)
+
+    # ---- SelfAwareEncoder at the Yelp shape --------------------------------------------------
+    nu, ni, L = args.users, args.items, args.layers
+    u, i = R.synthetic_incidence(nu, ni, args.edges, seed=0)
+    A = R.normalize_graph_mat(R.bipartite_adjacency(u, i, nu, ni))
+    data = types.SimpleNamespace(n_users=nu, n_items=ni, norm_adj=A, ui_adj=None)
+    adj = sparse_tensor_of(A, dev)
+    dropper = SpAdjDropEdge()
+    dropper.device_rng = True
+    for d in (64, 128):
+        torch.manual_seed(0)
+        ego = torch.nn.Parameter(torch.randn(nu + ni, d, device=dev) * 0.1)
+        dY = torch.randn(nu + ni, d, device=dev)
+        enc = SelfAwareEncoder(data, d, d, L, 0.1, 0.1, device=dev, use_self_att=False).train()
+
+        def step(gather_dtype, seed=None, enc=enc, ego=ego, dY=dY):
+            if seed is not None:
+                torch.manual_seed(seed)  # fixes the dropped edges
+            enc.gather_dtype = gather_dtype
+            ue, ie = enc(ego, dropper(adj, 0.5))
+            torch.autograd.backward([ue, ie], [dY[:nu], dY[nu:]])
+            out = [torch.cat([ue, ie]).detach(), ego.grad] + [p.grad for p in enc.parameters()
+                                                              if p.grad is not None]
+            ego.grad = None
+            for p in enc.parameters():
+                p.grad = None
+            return out
+
+        cases[f"self_aware_d{d}"] = (step, dict(users=nu, items=ni, edges=len(u), d=d, layers=L))
+
+    # ---- KHGRecRelationalAwareEncoder at the KHGRec.conf shape ---------------------------------
+    n, nr, B, d, dr, KL = (args.entities, args.relations, args.batch, args.kg_dim, args.rel_dim,
+                           args.kg_layers)
+    ku, kv = R.synthetic_incidence(n, n, args.kg_edges, seed=0)
+    kg = sp.csr_matrix((np.ones(len(ku), np.float32), (ku, kv)), shape=(n, n))
+    kg_adj = sparse_tensor_of(R.normalize_graph_mat(kg), dev)
+    rng = np.random.default_rng(1)
+    h, t, r = (torch.from_numpy(rng.integers(0, hi, B)).to(dev) for hi in (n, n, nr))
+    torch.manual_seed(0)
+    init = torch.nn.init.xavier_uniform_
+    kego = torch.nn.Parameter(init(torch.empty(n, d)).to(dev))
+    trans_M = init(torch.empty(nr, d, dr)).to(dev)
+    relation_emb = init(torch.empty(nr, dr)).to(dev)
+    kdY = torch.randn(n, d, device=dev)
+    kenc = KHGRecRelationalAwareEncoder(0.2, 0.1, KL, d).to(dev).train()
+    att = KGAttentionPattern(h, t, r, n, nr, validate=False).update(kego, trans_M, relation_emb)
+
+    def kstep(gather_dtype, seed=None):
+        kenc.gather_dtype = gather_dtype
+        y = kenc(kego, kg_adj, att)
+        y.backward(kdY)
+        out = [y.detach(), kego.grad] + [p.grad for p in kenc.parameters()]
+        kego.grad = None
+        for p in kenc.parameters():
+            p.grad = None
+        return out
+
+    cases["khgrec"] = (kstep, dict(entities=n, kg_nnz=len(ku), batch=B, d=d, layers=KL))
+
+    variants = [(f"{name}_{tag}", step, dt, info) for name, (step, info) in cases.items()
+                for tag, dt in (("f32", None), ("bf16", BF16))]
+    for _, step, dt, _ in variants:  # warm every shape
+        for _ in range(3):
+            step(dt)
+    torch.cuda.synchronize()
+    rounds = {name: [] for name, _, _, _ in variants}
+    for _ in range(args.rounds):
+        for name, step, dt, _ in variants:
+            ts = []
+            for _ in range(args.reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                step(dt)
+                e1.record()
+                e1.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            rounds[name].append(statistics.median(ts))
+    for name, _, dt, info in variants:
+        ms = rounds[name]
+        print(json.dumps({"variant": name, "gather_dtype": "bfloat16" if dt else None,
+                          "ms_fwd_bwd": round(statistics.median(ms), 4),
+                          "ms_min_round": round(min(ms), 4), "ms_max_round": round(max(ms), 4),
+                          "rounds": args.rounds, "reps": args.reps, **info}), flush=True)
+
+    def row_dev(a, b):
+        """(the largest row error relative to that row's largest |fp32| entry — the worst row,
+        often one whose sum nearly cancels; ‖a − b‖ / ‖b‖ over the whole table)."""
+        a, b = a.reshape(-1, a.shape[-1]).double(), b.reshape(-1, b.shape[-1]).double()
+        scale = b.abs().amax(dim=1).clamp_min(1e-30)
+        return (float(((a - b).abs().amax(dim=1) / scale).max()),
+                float((a - b).norm() / b.norm().clamp_min(1e-30)))
+
+    for name, (step, info) in cases.items():
+        f32 = [x.clone() for x in step(None, seed=7)]
+        b16 = [x.clone() for x in step(BF16, seed=7)]
+        names = ["out", "d_input"] + [f"d_param{k}" for k in range(len(f32) - 2)]
+        devs = {k: row_dev(a, b) for k, a, b in zip(names, b16, f32)}
+        print(json.dumps({"deviation": name,
+                          "bf16_vs_f32_max_row": {k: float(f"{v[0]:.3e}") for k, v in devs.items()},
+                          "bf16_vs_f32_fro": {k: float(f"{v[1]:.3e}") for k, v in devs.items()},
+                          **info}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,802 @@
+"""The fused row epilogue over bfloat16-gathered tables: hgd_spmm_fused_dt /
+hgd_spmm_masked_fused_dt, incidence.spmm_csr_fused_dt, the ``gather_dtype`` of
+functional.two_hop_fused / att_two_hop_fused and of the KG carriers' encoders.
+
+Statements, per result:
+  * forwarding: with an fp32 table and no bf16 copy the new entry points are hgd_spmm_fused /
+    hgd_spmm_masked_fused, bit for bit;
+  * bare store: without activation, LayerNorm, residual and with out_scale = 1 the fused hop is
+    spmm_csr(csr, M16, out_dtype=float32), bit for bit;
+  * the bf16 copy is torch's rounding of the fp32 rows, a second run is bitwise the first;
+  * the ops are, bit for bit, the calls they are made of (forward and backward);
+  * against the float64 oracle run on the bf16-rounded X, a value that passes through k bf16 stores
+    obeys |got - ref| <= (k·2^-9·2 + 1e-5)·Σ|terms| (tests/test_gpu_two_hop_bf16.py's derivation):
+    k = 1 for two_hop_fused (M, and dM in the backward), 3 for att_two_hop_fused (T, M, Z). Σ|terms|
+    is ``_check_rows`` of tests/test_gpu_fused.py restated with an rtol argument.
+
+``test_cpu_emulation_stays_inside_the_bounds`` needs no device: it runs the same cases through the
+oracle's hops with every intermediate rounded to bf16 by torch's CPU cast and checks them against
+the same bounds, so the bounds are known to hold for the arithmetic before a kernel is asked to.
+Its margins (largest error / bound over all cases): Y 0.25, dX 0.95, dγ 0.012, dβ 0.000; the
+LayerNorm cases need no looser factor (Y ≤ 0.05, dX ≤ 0.05). The kernels' margins, printed by the
+GPU tests, are the emulation's to two digits.
+
+One term of the dX bound is not in tests/test_gpu_fused.py, and comes from that emulation, not
+from a kernel: with an activation, act'(z) is read from the sign of z, and an element whose |z|
+lies inside the forward bound of zero has either sign once M is rounded, so its gradient may be
+its other branch's — an error of its whole magnitude, independent of the precision. Without the
+term the emulation itself leaves the k = 1 bound at the first LeakyReLU case (d = 8: 7 of 4,000
+elements of dX, 2.1e-2 of Σ|terms| against 3.9e-3). ``_check_rows`` therefore bounds exactly
+those elements (|z| ≤ rtol·Σ|terms of z|) by their full magnitude; every other element keeps
+rtol(k). The fp32 test has the same elements, 2^8 times fewer.
+"""
+import copy
+import ctypes
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import torch
+
+from oracle import hgd_oracle as O
+from tests._util import RTOL, assert_close, random_coo
+
+gpu = pytest.mark.gpu
+
+BF16, F32 = torch.bfloat16, torch.float32
+U_BF16 = 2.0 ** -9
+MARGIN = 2.0
+NV, NE = 500, 300
+WIDTHS = [8, 16, 64, 128, 256]  # groups of 1, 2, 8, 16 and 32 lanes (the widest LayerNorm row)
+UNALIGNED = [5, 20]            # one column per lane
+ATT_WIDTHS = [8, 64, 256, 20]
+OUT_SCALE, S1, S2 = 0.7, 1.0, 0.3
+# act, slope, residuals, split rows, weighted (tests/test_gpu_fused.py's four)
+COMBOS = [("leaky_relu", 0.2, 1, True, True), (None, 0.0, 2, False, False),
+          ("relu", 0.0, 0, True, False), ("leaky_relu", 0.5, 2, False, True)]
+
+
+def _rtol(k):
+    return k * U_BF16 * MARGIN + 1e-5
+
+
+def _bf16_round(a):
+    """float64 → the float64 image of torch's CPU float32 → bfloat16 cast."""
+    return torch.from_numpy(np.asarray(a, dtype=np.float32)).bfloat16().float().numpy().astype(
+        np.float64)
+
+
+# ---- the cases: structures, tables and their float64 operators -------------------------------
+def _coo(seed, split, empty_rows=False):
+    """~8,000 nonzeros on 500 × 300; with ``split`` row 7 holds every column (a split row under
+    split_threshold=32); with ``empty_rows`` every 7th row has none."""
+    rng = np.random.default_rng(seed)
+    r, c = random_coo(rng, NV, NE, 8000)
+    if split:
+        key = np.unique(np.concatenate([r * NE + c, 7 * NE + np.arange(NE)]))
+        r, c = key // NE, key % NE
+    if empty_rows:
+        keep = r % 7 != 0
+        r, c = r[keep], c[keep]
+    return r, c
+
+
+def _mat(rows, cols, w, shape):
+    return sp.csr_matrix((np.asarray(w, dtype=np.float64), (rows, cols)), shape=shape)
+
+
+class Chain:
+    """A linear operator as its hops in float64: ``fwd`` = [H1, …, Hk] (Z = Hk·…·H1·X, every
+    product but the last stored in bf16 on the device) and ``bwd`` the hops of its transpose in
+    the order the backward runs them."""
+
+    def __init__(self, fwd, bwd):
+        self.fwd, self.bwd = fwd, bwd
+
+    @staticmethod
+    def _run(hops, x, absolute=False, emulate=False):
+        x = np.abs(x) if absolute else np.asarray(x, dtype=np.float64)
+        for i, h in enumerate(hops):
+            x = (abs(h) if absolute else h) @ x
+            if emulate and i + 1 < len(hops):
+                x = _bf16_round(x)
+        return x
+
+    def forward(self, x, **kw):
+        return self._run(self.fwd, x, **kw)
+
+    def backward(self, dz, **kw):
+        return self._run(self.bwd, dz, **kw)
+
+
+def _two_hop_chain(r, c, vals, P, Q, R):
+    w = np.ones(len(r)) if vals is None else vals.astype(np.float64)
+    Ps, Qs, Rs = O._scale(r, w, NV, P), O._scale(c, w, NE, Q), O._scale(r, w, NV, R)
+    A = _mat(r, c, w, (NV, NE))
+    dg = sp.diags
+    # the device folds R (P in the backward) into the first hop's weights and applies Q as its
+    # row scale; the second hop's row scale is P (R)
+    return Chain([dg(Qs) @ A.T @ dg(Rs), dg(Ps) @ A], [dg(Qs) @ A.T @ dg(Ps), dg(Rs) @ A])
+
+
+def _make_case(d, act, slope, ln, n_res, seed, n_rows=NV):
+    rng = np.random.default_rng(seed)
+    o = dict(d=d, act=act, slope=slope, ln=ln, out_scale=OUT_SCALE, s1=S1, s2=S2)
+    o["X"] = rng.standard_normal((n_rows, d)).astype(np.float32)
+    o["res"] = [rng.standard_normal((n_rows, d)).astype(np.float32) for _ in range(n_res)]
+    o["dY"] = rng.standard_normal((n_rows, d)).astype(np.float32)
+    o["gamma"] = (rng.random(d) + 0.5).astype(np.float32) if ln else None
+    o["beta"] = rng.standard_normal(d).astype(np.float32) if ln else None
+    o["Xr"] = _bf16_round(o["X"])  # what the hops gather
+    return o
+
+
+def _two_hop_case(d, ln, i, masked=False, empty_rows=False):
+    act, slope, n_res, split, weighted = COMBOS[i]
+    seed = 100 * d + 10 * i + ln + (1000 if masked else 0) + (2000 if empty_rows else 0)
+    r, c = _coo(seed, split, empty_rows)
+    rng = np.random.default_rng(seed + 1)
+    vals = (rng.random(len(r)) + 0.1).astype(np.float32) if weighted or masked else None
+    P, Q, R = (None, None, None) if weighted or masked else ("mean", "mean", None)
+    o = _make_case(d, act, slope, ln, n_res, seed + 2)
+    o.update(r=r, c=c, vals=vals, P=P, Q=Q, R=R, split=split, k=1)
+    if masked:  # SpAdjDropEdge's matrix: the kept edges, vals / keep (keep = 0.5 is exact)
+        o["mask"] = rng.random(len(r)) < 0.5
+        o["chain"] = _two_hop_chain(r[o["mask"]], c[o["mask"]], vals[o["mask"]] / np.float32(0.5),
+                                    P, Q, R)
+    else:
+        o["chain"] = _two_hop_chain(r, c, vals, P, Q, R)
+    return o
+
+
+N_ATT, M_ATT, C_ATT = 300, 200, 120
+
+
+def _att_case(d, ln, i):
+    """att [300, 200] row-stochastic with empty rows, K [200, 120] weighted; Z = att·K·Kᵀ·attᵀ·X."""
+    act, slope, n_res, split, _ = COMBOS[i]
+    seed = 7000 + 100 * d + 10 * i + ln
+    rng = np.random.default_rng(seed)
+    ar, ac = random_coo(rng, N_ATT, M_ATT, 1500)
+    keep = ar % 11 != 0  # rows without entries: z = 0, the row is β plus the residual
+    ar, ac = ar[keep], ac[keep]
+    if split:  # one row of att long enough to split
+        key = np.unique(np.concatenate([ar * M_ATT + ac, 5 * M_ATT + np.arange(M_ATT)]))
+        ar, ac = key // M_ATT, key % M_ATT
+    aw = rng.random(len(ar)) + 0.1
+    aw = (aw / np.bincount(ar, weights=aw, minlength=N_ATT)[ar]).astype(np.float32)
+    kr, kc = random_coo(rng, M_ATT, C_ATT, 1200)
+    kw = (rng.random(len(kr)) + 0.1).astype(np.float32)
+    o = _make_case(d, act, slope, ln, n_res, seed + 2, n_rows=N_ATT)
+    A, K = _mat(ar, ac, aw, (N_ATT, M_ATT)), _mat(kr, kc, kw, (M_ATT, C_ATT))
+    hops = [A.T.tocsr(), K.T.tocsr(), K, A]
+    o.update(att=(ar, ac, aw), kg=(kr, kc, kw), split=split, k=3, chain=Chain(hops, hops))
+    return o
+
+
+# ---- the bounds -------------------------------------------------------------------------------
+def _check_rows(o, got, rtol):
+    """tests/test_gpu_fused.py's ``_check_rows`` with the relative bound as an argument: the
+    fused row epilogue over the linear operator ``o['chain']`` — Y, dX, the residual gradients,
+    dγ and dβ against the float64 oracle on the bf16-rounded X, each bound scaled by the
+    magnitude of its sum. Returns the largest error / bound ratio per quantity."""
+    ch, act, slope, ln = o["chain"], o["act"], o["slope"], o["ln"]
+    Z = ch.forward(o["Xr"])
+    magz = ch.forward(o["Xr"], absolute=True)
+    gamma = beta = None
+    if ln:
+        gamma, beta = o["gamma"].astype(np.float64), o["beta"].astype(np.float64)
+    res = o["res"]
+    Yref, a = O.row_epilogue(Z, act, slope, ln, gamma, beta, 1e-5, o["out_scale"],
+                             res[0] if res else None, o["s1"],
+                             res[1] if len(res) > 1 else None, o["s2"])
+    if ln:
+        rstd = 1.0 / np.sqrt(a.var(-1, keepdims=True) + 1e-5)
+        m = (magz + magz.mean(-1, keepdims=True)) * rstd * 4
+        mag = o["out_scale"] * (m * np.abs(gamma) + np.abs(beta))
+    else:
+        mag = o["out_scale"] * magz
+    for k, s in zip(range(len(res)), (o["s1"], o["s2"])):
+        mag = mag + abs(s) * np.abs(res[k])
+    ratios = {}
+
+    def close(what, g, ref, m, rt):
+        err = np.abs(np.asarray(g, dtype=np.float64) - ref)
+        ratios[what] = float(np.max(err / (rt * m + 1e-30)))
+        assert_close(g, ref, m, rtol=rt, what=f"fused bf16 {what}")
+
+    close("Y", got["Y"], Yref, mag, rtol)
+    dZ, dg, db = O.row_epilogue_backward(Z, o["dY"], act, slope, ln, gamma, 1e-5, o["out_scale"])
+    dX = ch.backward(dZ)
+    dy = o["out_scale"] * np.abs(o["dY"])
+    if ln:
+        ah = np.abs(a - a.mean(-1, keepdims=True)) * rstd
+        gh = dy * np.abs(gamma)
+        mdz = rstd * (gh + gh.mean(-1, keepdims=True) + ah * (gh * ah).mean(-1, keepdims=True)) * 8
+        mdz = mdz + np.abs(dZ) * 8 * magz * rstd  # LN conditioning on the error of a
+    else:
+        mdz = dy
+    if act == "leaky_relu":
+        mdz = mdz * max(1.0, slope)
+    if act is not None:
+        # act'(z) is read from the sign of a computed z: where |z| is inside the forward bound of
+        # zero, the computed sign is either one, and the element's gradient is its other branch's
+        # — an error of up to its whole magnitude, whatever the precision (the fp32 test meets
+        # the same elements, 2^8 times fewer). Those elements are bounded by mdz itself.
+        mdz = np.where(np.abs(Z) <= rtol * magz, mdz / rtol, mdz)
+    dmag = ch.backward(mdz, absolute=True)
+    close("dX", got["dX"], dX, dmag, rtol)
+    for k, s in zip(range(len(res)), (o["s1"], o["s2"])):
+        if "dres" in got:  # (exact: fp32, untouched by the option)
+            np.testing.assert_array_equal(got["dres"][k], (np.float32(s) * o["dY"]) if s != 1.0
+                                          else o["dY"])
+    if ln:
+        close("dgamma", got["dgamma"], dg, (dy * ah).sum(0) * 8 + 1e-6, rtol)
+        close("dbeta", got["dbeta"], db, dy.sum(0) * 2, RTOL)  # an fp32 sum of dY: no bf16 in it
+    return ratios
+
+
+def _emulate(o):
+    """The device path in float64 with every bf16 store a torch CPU cast: the hops' intermediates
+    in the forward and in the backward; the epilogue and its gradient exact."""
+    ch, act, slope, ln = o["chain"], o["act"], o["slope"], o["ln"]
+    gamma = beta = None
+    if ln:
+        gamma, beta = o["gamma"].astype(np.float64), o["beta"].astype(np.float64)
+    res = o["res"]
+    Z = ch.forward(o["Xr"], emulate=True)
+    Y, _ = O.row_epilogue(Z, act, slope, ln, gamma, beta, 1e-5, o["out_scale"],
+                          res[0] if res else None, o["s1"], res[1] if len(res) > 1 else None,
+                          o["s2"])
+    dZ, dg, db = O.row_epilogue_backward(Z, o["dY"], act, slope, ln, gamma, 1e-5, o["out_scale"])
+    return dict(Y=Y, dX=ch.backward(dZ, emulate=True), dgamma=dg, dbeta=db)
+
+
+def _all_cases():
+    for d in WIDTHS + UNALIGNED:
+        for ln in (False, True):
+            for i in range(len(COMBOS)):
+                yield f"two_hop d={d} ln={ln} combo={i}", lambda d=d, ln=ln, i=i: _two_hop_case(
+                    d, ln, i)
+    for d in ATT_WIDTHS:
+        for ln in (False, True):
+            for i in (0, 1):
+                yield f"att d={d} ln={ln} combo={i}", lambda d=d, ln=ln, i=i: _att_case(d, ln, i)
+    yield "wide row", lambda: _two_hop_case(320, False, 0)
+    yield "masked", lambda: _two_hop_case(64, True, 0, masked=True)
+    yield "empty rows", lambda: _two_hop_case(64, True, 3, empty_rows=True)
+
+
+def test_cpu_emulation_stays_inside_the_bounds():
+    """Every case of this file through the emulation, against the bounds the kernels are held
+    to; prints the margins (largest error / bound)."""
+    worst = {}
+    for name, make in _all_cases():
+        o = make()
+        ratios = _check_rows(o, _emulate(o), _rtol(o["k"]))
+        print(f"emulation {name}: " + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+        for k, v in ratios.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    print("emulation, largest error / bound: "
+          + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+    assert all(v <= 1.0 for v in worst.values())
+
+
+# ---- device helpers -----------------------------------------------------------------------------
+def _inc(r, c, vals, shape, dev, **kw):
+    from hypergraph_diffusion_for_recommendation_amd import Incidence
+    idx = torch.from_numpy(np.stack([r, c]).astype(np.int64))
+    v = None if vals is None else torch.from_numpy(np.asarray(vals, dtype=np.float32))
+    return Incidence.from_coo(idx, v, shape, device=dev, **kw)
+
+
+def _split_kw(split):
+    return dict(split_threshold=32, split_chunk=16) if split else dict(split_threshold=0)
+
+
+def _norm(o, dev):
+    if not o["ln"]:
+        return None
+    norm = torch.nn.LayerNorm(o["d"]).to(dev)
+    with torch.no_grad():
+        norm.weight.copy_(torch.from_numpy(o["gamma"]))
+        norm.bias.copy_(torch.from_numpy(o["beta"]))
+    return norm
+
+
+def _t(a, dev, grad=False):
+    return torch.from_numpy(a).to(dev).requires_grad_(grad)
+
+
+def _epilogue_desc(o, n, dev, norm, res):
+    """The descriptor of the case's epilogue and the buffers it writes (act_out, stats)."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    epi = {None: nat.EPI_NONE, "leaky_relu": nat.EPI_LEAKY_RELU, "relu": nat.EPI_RELU}[o["act"]]
+    ln, d = o["ln"], o["d"]
+    A = torch.empty((n, d), device=dev) if ln or epi != nat.EPI_NONE else None
+    stats = torch.empty((n, 2), device=dev) if ln else None
+    ex = nat.RowEpilogue(
+        act=epi, slope=o["slope"], layer_norm=int(ln), ln_eps=1e-5,
+        ln_gamma=norm.weight.data_ptr() if ln else None,
+        ln_beta=norm.bias.data_ptr() if ln else None, out_scale=o["out_scale"],
+        res1=res[0].data_ptr() if len(res) > 0 else None, ld_res1=d if len(res) > 0 else 0,
+        res1_scale=o["s1"], res2=res[1].data_ptr() if len(res) > 1 else None,
+        ld_res2=d if len(res) > 1 else 0, res2_scale=o["s2"],
+        act_out=nat.ptr(A), ld_act=d if A is not None else 0, stats=nat.ptr(stats))
+    return ex, epi, A, stats
+
+
+def _epilogue_backward(o, epi, A, stats, norm, dY):
+    """hgd_row_epilogue_backward as the ops call it; a pure blend launches nothing and leaves
+    the factor out_scale to the first backward hop."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    lib = nat.load()
+    n, d = dY.shape
+    if not o["ln"] and epi == nat.EPI_NONE:
+        return dY, o["out_scale"], None, None
+    dg = torch.empty(d, device=dY.device) if o["ln"] else None
+    db = torch.empty(d, device=dY.device) if o["ln"] else None
+    wsb = lib.hgd_row_epilogue_backward_workspace_size(n, d) if o["ln"] else 0
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dY.device) if wsb else None
+    dZ = torch.empty_like(dY)
+    nat.check(lib.hgd_row_epilogue_backward(
+        dY.data_ptr(), dY.stride(0), nat.ptr(A), 0 if A is None else A.stride(0), nat.ptr(stats),
+        norm.weight.data_ptr() if o["ln"] else None, n, d, epi, o["slope"], int(o["ln"]),
+        o["out_scale"], dZ.data_ptr(), dZ.stride(0), nat.ptr(dg), nat.ptr(db), nat.ptr(ws), wsb,
+        nat.stream_handle(dY.device)), "hgd_row_epilogue_backward")
+    return dZ, 1.0, dg, db
+
+
+def _kw(o, norm, rt):
+    return dict(epilogue=o["act"], slope=o["slope"], norm=norm, out_scale=o["out_scale"],
+                res1=rt[0] if len(rt) > 0 else None, res1_scale=o["s1"],
+                res2=rt[1] if len(rt) > 1 else None, res2_scale=o["s2"])
+
+
+def _got(Y, grads, n_res, ln):
+    g = [x.detach().cpu().numpy() for x in grads]
+    out = dict(Y=Y.detach().cpu().numpy(), dX=g[0], dres=g[1:1 + n_res])
+    if ln:
+        out.update(dgamma=g[1 + n_res], dbeta=g[2 + n_res])
+    return out
+
+
+def _run_two_hop(o, dev):
+    """two_hop_fused(gather_dtype=bf16, return_x16=True) forward + backward, twice (determinism),
+    against the calls it is made of and the oracle."""
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr, spmm_csr_fused_dt
+    from hypergraph_diffusion_for_recommendation_amd.functional import two_hop_fused
+    inc = _inc(o["r"], o["c"], o["vals"], (NV, NE), dev, **_split_kw(o["split"]))
+    assert (inc.csr.n_heavy > 0) == o["split"]
+    if "mask" in o:
+        inc = inc.masked(torch.from_numpy(o["mask"]), 0.5)
+    P, Q, R = o["P"], o["Q"], o["R"]
+    norm = _norm(o, dev)
+    dY = _t(o["dY"], dev)
+
+    def run():
+        Xt = _t(o["X"], dev, True)
+        rt = [_t(x, dev, True) for x in o["res"]]
+        Y, Y16 = two_hop_fused(inc, Xt, P=P, Q=Q, R=R, gather_dtype=BF16, return_x16=True,
+                               **_kw(o, norm, rt))
+        assert Y.dtype == F32 and Y16.dtype == BF16 and not Y16.requires_grad
+        params = [Xt] + rt + ([norm.weight, norm.bias] if o["ln"] else [])
+        grads = torch.autograd.grad(Y, params, dY)
+        assert all(g.dtype == F32 for g in grads)
+        return Y.detach(), Y16, grads
+
+    Y, Y16, grads = run()
+    assert torch.equal(Y16, Y.bfloat16())
+    Y2, Y16b, grads2 = run()
+    assert torch.equal(Y, Y2) and torch.equal(Y16, Y16b)
+    assert all(torch.equal(a, b) for a, b in zip(grads, grads2))
+    # a caller's x16 is the cast the op makes itself; without return_x16 Y is the same
+    Y3 = two_hop_fused(inc, _t(o["X"], dev), P=P, Q=Q, R=R, gather_dtype=BF16,
+                       x16=_t(o["X"], dev).bfloat16(),
+                       **_kw(o, norm, [_t(x, dev) for x in o["res"]]))
+    assert torch.equal(Y3, Y)
+    # the calls it is made of
+    X16 = _t(o["X"], dev).bfloat16()
+    res = [_t(x, dev) for x in o["res"]]
+    q = inc.scale("col", Q)
+    M16 = spmm_csr(inc.csc, X16, val=inc.edge_values("csc", R), row_scale=q)
+    assert M16.dtype == BF16
+    ex, epi, A, stats = _epilogue_desc(o, NV, dev, norm, res)
+    Yc16 = torch.empty((NV, o["d"]), dtype=BF16, device=dev)
+    Yc = spmm_csr_fused_dt(inc.csr, M16, ex, val=inc.val, row_scale=inc.scale("row", P),
+                           out16=Yc16)
+    assert torch.equal(Y, Yc) and torch.equal(Y16, Yc16)
+    dZ, dz_scale, dg, db = _epilogue_backward(o, epi, A, stats, norm, dY)
+    if dz_scale != 1.0:
+        q = (torch.full((NE,), dz_scale, device=dev) if q is None else q * dz_scale)
+    dM16 = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q, out_dtype=BF16)
+    dXc = spmm_csr(inc.csr, dM16, val=inc.val, row_scale=inc.scale("row", R), out_dtype=F32)
+    assert torch.equal(grads[0], dXc)
+    if o["ln"]:
+        assert torch.equal(grads[-2], dg) and torch.equal(grads[-1], db)
+    ratios = _check_rows(o, _got(Y, grads, len(o["res"]), o["ln"]), _rtol(1))
+    print(f"two_hop_fused bf16 d={o['d']}: " + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+    return inc, Y
+
+
+# ---- 1. forwarding ----------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
+def test_f32_without_a_copy_forwards_bitwise(dev, masked):
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    lib = nat.load()
+    o = _two_hop_case(64, True, 0)
+    inc = _inc(o["r"], o["c"], o["vals"], (NV, NE), dev, **_split_kw(True))
+    assert inc.csr.n_heavy > 0
+    csr = inc.csr
+    mask = torch.from_numpy(np.random.default_rng(5).random(csr.nnz) < 0.5).to(dev).to(
+        torch.uint8)
+    norm, res = _norm(o, dev), [_t(x, dev) for x in o["res"]]
+    M = torch.from_numpy(np.random.default_rng(6).standard_normal((NE, 64)).astype(
+        np.float32)).to(dev)
+    plan = ctypes.byref(csr.plan)
+    wsb = lib.hgd_spmm_workspace_size(plan, 64)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    st = nat.stream_handle(dev)
+    outs = []
+    for dt in (False, True):
+        ex, _, A, stats = _epilogue_desc(o, NV, dev, norm, res)
+        Y = torch.empty((NV, 64), device=dev)
+        head = [csr.rowptr.data_ptr(), csr.col.data_ptr(), inc.val.data_ptr()]
+        if masked:
+            head += [mask.data_ptr(), 0.5]
+        head += [None, NV, NE, 0, NV, M.data_ptr()]
+        tail = [plan, ws.data_ptr(), wsb, st]
+        name = "hgd_spmm_masked_fused" if masked else "hgd_spmm_fused"
+        if dt:
+            args = head + [nat.DT_F32, 64, Y.data_ptr(), 64, 64, ctypes.byref(ex), None, 0] + tail
+            name += "_dt"
+        else:
+            args = head + [64, Y.data_ptr(), 64, 64, ctypes.byref(ex)] + tail
+        nat.check(getattr(lib, name)(*args), name)
+        outs.append((Y, A, stats))
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+
+
+# ---- 2. the bare store --------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("d", WIDTHS + UNALIGNED)
+def test_bare_store_is_the_plain_bf16_hop(dev, d):
+    """No activation, LayerNorm or residual, out_scale = 1, no split rows: bitwise the plain
+    bf16 → f32 hop (at d = 256 that one runs two 128-column passes, the fused one a single pass:
+    the per-column sums do not depend on it), and the copy is its rounding."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr, spmm_csr_fused_dt
+    r, c = _coo(d, split=False)
+    rng = np.random.default_rng(d)
+    inc = _inc(r, c, rng.random(len(r)) + 0.1, (NV, NE), dev, split_threshold=0)
+    assert inc.csr.n_heavy == 0
+    M16 = torch.from_numpy(rng.standard_normal((NE, d)).astype(np.float32)).to(dev).bfloat16()
+    s = inc.scale("row", "mean")
+    for val, scale in ((inc.val, None), (None, s)):
+        ref = spmm_csr(inc.csr, M16, val=val, row_scale=scale, out_dtype=F32)
+        Y16 = torch.empty((NV, d), dtype=BF16, device=dev)
+        Y = spmm_csr_fused_dt(inc.csr, M16, nat.RowEpilogue(out_scale=1.0), val=val,
+                              row_scale=scale, out16=Y16)
+        assert Y.dtype == F32 and torch.equal(Y, ref)
+        assert torch.equal(Y16, ref.bfloat16())
+        assert torch.equal(spmm_csr_fused_dt(inc.csr, M16, nat.RowEpilogue(out_scale=1.0),
+                                             val=val, row_scale=scale), ref)
+
+
+# ---- 3.–6. the ops: copy, determinism, composition, oracle bounds ---------------------------------
+@gpu
+@pytest.mark.parametrize("d", WIDTHS + UNALIGNED)
+@pytest.mark.parametrize("ln", [False, True])
+def test_two_hop_fused_bf16(dev, d, ln):
+    for i in range(len(COMBOS)):
+        _run_two_hop(_two_hop_case(d, ln, i), dev)
+
+
+@gpu
+def test_two_hop_fused_bf16_wide_row(dev):
+    """d = 320 without LayerNorm (with it the op takes the unfused composition): the fused store
+    over a bf16 table runs a 256-column pass of 32 lanes and a second one over the last 64."""
+    _run_two_hop(_two_hop_case(320, False, 0), dev)
+
+
+@gpu
+def test_two_hop_fused_bf16_masked_structure(dev):
+    """An edge-dropped view (hgd_spmm_masked_dt, hgd_spmm_masked_fused_dt) with split rows,
+    against the oracle over the dropped matrix."""
+    _run_two_hop(_two_hop_case(64, True, 0, masked=True), dev)
+
+
+@gpu
+def test_two_hop_fused_bf16_empty_rows(dev):
+    """Rows without nonzeros: z = 0, so LayerNorm yields β and the row is out_scale·β + res1 +
+    s2·res2, in the kernel's operation order."""
+    o = _two_hop_case(64, True, 3, empty_rows=True)
+    _, Y = _run_two_hop(o, dev)
+    empty = np.setdiff1d(np.arange(NV), o["r"])
+    assert len(empty) >= NV // 7
+    # three fp32 operations (β·out_scale and two fused multiply-adds), each within 2^-24 of its
+    # result: 3·2^-24 of the terms' magnitude, taken as 4
+    terms = [OUT_SCALE * o["beta"].astype(np.float64)[None, :], S1 * o["res"][0][empty],
+             np.float64(np.float32(S2)) * o["res"][1][empty]]
+    want, mag = sum(terms), sum(np.abs(t) for t in terms)
+    assert_close(Y.cpu().numpy()[empty], want, mag, rtol=4 * 2.0 ** -24, what="empty rows")
+
+
+@gpu
+@pytest.mark.parametrize("d,ln", [(5, True), (20, True), (64, False)])
+def test_fused_hop_over_column_offset_views(dev, d, ln):
+    """The table, the output, the residual and the copy as views one column into wider
+    matrices: every row starts off the 16-byte grid, so the hop takes one column per lane (at
+    d = 64 too). Bitwise the same call over contiguous copies; the bytes around the views stay.
+    At d = 64 the contiguous call runs 8-column lanes, so only what does not depend on the lanes
+    per row is compared: no LayerNorm (its statistics are a butterfly over the group) and no
+    split rows (the fix-up's combine order follows the group size)."""
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr_fused_dt
+    o = _two_hop_case(d, ln, 0)
+    split = d != 64
+    r, c = (o["r"], o["c"]) if split else _coo(d, split=False)
+    vals = np.random.default_rng(d + 1).random(len(r)) + 0.1
+    inc = _inc(r, c, vals, (NV, NE), dev, **_split_kw(split))
+    assert (inc.csr.n_heavy > 0) == split
+    norm = _norm(o, dev)
+    rng = np.random.default_rng(d)
+    M = torch.from_numpy(rng.standard_normal((NE, d)).astype(np.float32)).to(dev).bfloat16()
+    res = _t(o["res"][0], dev)
+
+    def view(t, rows, fill):
+        w = torch.full((rows, d + 1), fill, dtype=t.dtype, device=dev)
+        w[:, 1:] = t
+        return w, w[:, 1:]
+
+    ex, _, A, stats = _epilogue_desc(o, NV, dev, norm, [res])
+    Y16 = torch.empty((NV, d), dtype=BF16, device=dev)
+    Y = spmm_csr_fused_dt(inc.csr, M, ex, val=inc.val, out16=Y16)
+    Mw, Mv = view(M, NE, 3.0)
+    Rw, Rv = view(res, NV, 5.0)
+    Yw, Yv = view(torch.zeros((NV, d), device=dev), NV, 7.0)
+    Hw, Hv = view(torch.zeros((NV, d), dtype=BF16, device=dev), NV, 9.0)
+    exv, _, Av, statsv = _epilogue_desc(o, NV, dev, norm, [res])
+    exv.res1, exv.ld_res1 = Rv.data_ptr(), d + 1
+    out = spmm_csr_fused_dt(inc.csr, Mv, exv, val=inc.val, out=Yv, out16=Hv)
+    assert out is Yv
+    assert torch.equal(Yv, Y) and torch.equal(Hv, Y16) and torch.equal(Hv, Y.bfloat16())
+    assert torch.equal(Av, A) and (not ln or torch.equal(statsv, stats))
+    assert bool((Yw[:, 0] == 7.0).all()) and bool((Hw[:, 0] == 9.0).all())
+
+
+@gpu
+def test_fused_hop_row_range(dev):
+    """Rows [100, 333) only (one of them split): bitwise those rows of the full call, everything
+    outside the range untouched in Y, the copy, act_out and the statistics."""
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr_fused_dt
+    o = _two_hop_case(64, True, 0)
+    r = np.concatenate([o["r"], np.full(NE, 200)])
+    c = np.concatenate([o["c"], np.arange(NE)])
+    key = np.unique(r * NE + c)
+    r, c = key // NE, key % NE
+    rng = np.random.default_rng(11)
+    inc = _inc(r, c, rng.random(len(r)) + 0.1, (NV, NE), dev, **_split_kw(True))
+    assert inc.csr.n_heavy >= 2  # rows 7 (outside the range) and 200 (inside)
+    norm, res = _norm(o, dev), [_t(o["res"][0], dev)]
+    M = torch.from_numpy(rng.standard_normal((NE, 64)).astype(np.float32)).to(dev).bfloat16()
+    ex, _, A, stats = _epilogue_desc(o, NV, dev, norm, res)
+    Y16 = torch.empty((NV, 64), dtype=BF16, device=dev)
+    Y = spmm_csr_fused_dt(inc.csr, M, ex, val=inc.val, out16=Y16)
+    ex2, _, A2, stats2 = _epilogue_desc(o, NV, dev, norm, res)
+    A2.fill_(-3.0)
+    stats2.fill_(-3.0)
+    Yp = torch.full((NV, 64), -3.0, device=dev)
+    Yp16 = torch.full((NV, 64), -3.0, dtype=BF16, device=dev)
+    spmm_csr_fused_dt(inc.csr, M, ex2, val=inc.val, out=Yp, out16=Yp16, row_begin=100,
+                      row_end=333)
+    for full, part in ((Y, Yp), (Y16, Yp16), (A, A2), (stats, stats2)):
+        assert torch.equal(part[100:333], full[100:333])
+        assert bool((part[:100] == -3.0).all()) and bool((part[333:] == -3.0).all())
+
+
+@gpu
+@pytest.mark.parametrize("d", ATT_WIDTHS)
+@pytest.mark.parametrize("ln", [False, True])
+def test_att_two_hop_fused_bf16(dev, d, ln):
+    from hypergraph_diffusion_for_recommendation_amd import spmm_csr, spmm_csr_fused_dt
+    from hypergraph_diffusion_for_recommendation_amd.functional import att_two_hop_fused
+    for i in (0, 1):
+        o = _att_case(d, ln, i)
+        att = _inc(*o["att"], (N_ATT, M_ATT), dev, **_split_kw(o["split"]))
+        inc = _inc(*o["kg"], (M_ATT, C_ATT), dev)
+        assert (att.csr.n_heavy > 0) == o["split"]
+        norm = _norm(o, dev)
+        dY = _t(o["dY"], dev)
+
+        def run():
+            Xt = _t(o["X"], dev, True)
+            rt = [_t(x, dev, True) for x in o["res"]]
+            Y, Y16 = att_two_hop_fused(att, inc, Xt, gather_dtype=BF16, return_x16=True,
+                                       **_kw(o, norm, rt))
+            assert Y.dtype == F32 and Y16.dtype == BF16 and not Y16.requires_grad
+            params = [Xt] + rt + ([norm.weight, norm.bias] if ln else [])
+            grads = torch.autograd.grad(Y, params, dY)
+            assert all(g.dtype == F32 for g in grads)
+            return Y.detach(), Y16, grads
+
+        Y, Y16, grads = run()
+        assert torch.equal(Y16, Y.bfloat16())
+        Y2, Y16b, grads2 = run()
+        assert torch.equal(Y, Y2) and torch.equal(Y16, Y16b)
+        assert all(torch.equal(a, b) for a, b in zip(grads, grads2))
+
+        def hops(X, first):  # K·(Kᵀ·(attᵀ·X)), stored in bf16
+            T = spmm_csr(att.csc, X, val=att.val_t, out_dtype=first)
+            M = spmm_csr(inc.csc, T, val=inc.val_t)
+            Z = spmm_csr(inc.csr, M, val=inc.val)
+            assert T.dtype == M.dtype == Z.dtype == BF16
+            return Z
+
+        res = [_t(x, dev) for x in o["res"]]
+        ex, epi, A, stats = _epilogue_desc(o, N_ATT, dev, norm, res)
+        Yc16 = torch.empty((N_ATT, d), dtype=BF16, device=dev)
+        Yc = spmm_csr_fused_dt(att.csr, hops(_t(o["X"], dev).bfloat16(), None), ex, val=att.val,
+                               out16=Yc16)
+        assert torch.equal(Y, Yc) and torch.equal(Y16, Yc16)
+        dZ, dz_scale, dg, db = _epilogue_backward(o, epi, A, stats, norm, dY)
+        if dz_scale != 1.0:
+            dZ = dZ * dz_scale
+        dXc = spmm_csr(att.csr, hops(dZ, BF16), val=att.val, out_dtype=F32)
+        assert torch.equal(grads[0], dXc)
+        if ln:
+            assert torch.equal(grads[-2], dg) and torch.equal(grads[-1], db)
+        ratios = _check_rows(o, _got(Y, grads, len(o["res"]), ln), _rtol(3))
+        print(f"att_two_hop_fused bf16 d={d}: "
+              + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+        empty = np.setdiff1d(np.arange(N_ATT), o["att"][0])
+        assert len(empty) > 0
+
+
+@gpu
+@pytest.mark.parametrize("op", ["two_hop_fused", "att_two_hop_fused"])
+def test_unfusable_shapes_take_the_unfused_bf16_composition(dev, op):
+    """LayerNorm at d = 320, LayerNorm at d = 100 and 68 (d % 8 == 4: the fp32 fused store holds
+    them, the bf16 one has no 8-column lanes for them and no LayerNorm above 64 one-column lanes)
+    and a negative slope: the hops over X.bfloat16() into an fp32 result, then the torch
+    epilogue — fp32 results and gradients, the copy torch's rounding."""
+    from hypergraph_diffusion_for_recommendation_amd import functional as F
+    for d, slope in ((320, 0.2), (100, 0.2), (68, 0.2), (64, -0.5)):
+        o = (_two_hop_case if op == "two_hop_fused" else _att_case)(64, True, 0)
+        rng = np.random.default_rng(d)
+        norm = torch.nn.LayerNorm(d).to(dev)
+        if op == "two_hop_fused":
+            inc = _inc(o["r"], o["c"], o["vals"], (NV, NE), dev)
+            n = NV
+
+            def f(X, **kw):
+                return F.two_hop_fused(inc, X, **kw)
+
+            def hop(X16):
+                return F.two_hop(inc, X16, epilogue="leaky_relu", slope=slope, out_dtype=F32)
+        else:
+            att = _inc(*o["att"], (N_ATT, M_ATT), dev)
+            inc = _inc(*o["kg"], (M_ATT, C_ATT), dev)
+            n = N_ATT
+
+            def f(X, **kw):
+                return F.att_two_hop_fused(att, inc, X, **kw)
+
+            def hop(X16):
+                from hypergraph_diffusion_for_recommendation_amd import spmm_csr
+                Z = F._att_hops(att, inc, X16)
+                Y = spmm_csr(att.csr, Z, val=att.val, out_dtype=F32)
+                return torch.where(Y > 0, Y, Y * slope)
+        X = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+        res = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+        Xg = X.clone().requires_grad_(True)
+        Y, Y16 = f(Xg, epilogue="leaky_relu", slope=slope, norm=norm, res1=res,
+                   gather_dtype=BF16, return_x16=True)
+        (dX,) = torch.autograd.grad(Y, Xg, torch.ones_like(Y))
+        assert Y.dtype == F32 and dX.dtype == F32 and bool(dX.abs().sum() > 0)
+        assert torch.equal(Y16, Y.detach().bfloat16()) and not Y16.requires_grad
+        want = norm(hop(X.bfloat16())) + res
+        assert torch.equal(Y.detach(), want.detach())
+
+
+# ---- 7. the encoders ----------------------------------------------------------------------------
+def _encoder_case(kind, n_layers, dev):
+    """``enc, call(enc, x), chain(enc, x, gather_dtype)``: the encoder, its forward, and the
+    explicit per-layer chain of the ops with the copy handed on (the residual's uses through
+    functional.fan, as the encoders take them)."""
+    from hypergraph_diffusion_for_recommendation_amd import encoders as E
+    from hypergraph_diffusion_for_recommendation_amd import functional as F
+    d, slope = 64, 0.2
+    rng = np.random.default_rng(40 + n_layers)
+    torch.manual_seed(n_layers)
+    if kind == "self":
+        U, I = 60, 45
+        u, i = random_coo(rng, U, I, 400)
+        w = (rng.random(len(u)) + 0.1).astype(np.float32)
+        n = U + I
+        rows, cols = np.concatenate([u, i + U]), np.concatenate([i + U, u])
+        inc = _inc(rows, cols, np.tile(w, 2), (n, n), dev)
+        data = SimpleNamespace(n_users=U, n_items=I, norm_adj=None)
+        enc = E.SelfAwareEncoder(data, d, d, n_layers, slope, 0.1, device=dev,
+                                 use_self_att=False)
+
+        def call(e, x):
+            return torch.cat(e(x, inc))
+    else:
+        n, m = 90, 40
+        r, c = random_coo(rng, n, m, 500)
+        inc = _inc(r, c, rng.random(len(r)) + 0.1, (n, m), dev)
+        if kind == "relational":
+            enc = E.RelationalAwareEncoder(slope, 0.1, n_layers, d).to(dev)
+
+            def call(e, x):
+                return e(x, inc, None)
+        else:
+            ar, ac = random_coo(rng, n, n, 400)
+            aw = rng.random(len(ar)) + 0.1
+            att = _inc(ar, ac, aw / np.bincount(ar, weights=aw, minlength=n)[ar], (n, n), dev)
+            enc = E.KHGRecRelationalAwareEncoder(slope, 0.1, n_layers, d).to(dev)
+
+            def call(e, x):
+                return e(x, inc, att)
+    with torch.no_grad():
+        for ln in enc.lns:
+            ln.weight.uniform_(0.5, 1.5)
+            ln.bias.uniform_(-0.2, 0.2)
+
+    def chain(e, x, gather_dtype):
+        L = n_layers
+        uses = F.fan(x, L + 1)
+        y, res, y16 = uses[0], uses[1:], None
+        for k in range(L):
+            kw = dict(epilogue=None if k == L - 1 else "leaky_relu", slope=slope, norm=e.lns[k],
+                      res1=res[k], res1_scale=1.0)
+            if gather_dtype is not None:
+                kw.update(gather_dtype=gather_dtype, x16=y16, return_x16=k < L - 1)
+            out = (F.att_two_hop_fused(att, inc, y, **kw) if kind == "khgrec"
+                   else F.two_hop_fused(inc, y, **kw))
+            y, y16 = out if kw.get("return_x16") else (out, None)
+        return y
+
+    x = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+    w = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+    return enc, call, chain, x, w
+
+
+def _fwd_bwd(enc, f, x, w):
+    for p in enc.parameters():
+        p.grad = None
+    xg = x.clone().requires_grad_(True)
+    y = f(enc, xg)
+    (y * w).sum().backward()
+    return [y.detach(), xg.grad] + [p.grad.clone() for p in enc.lns.parameters()]
+
+
+@gpu
+@pytest.mark.parametrize("n_layers", [2, 3])
+@pytest.mark.parametrize("kind", ["self", "relational", "khgrec"])
+def test_encoders_gather_dtype(dev, kind, n_layers):
+    enc, call, chain, x, w = _encoder_case(kind, n_layers, dev)
+    assert enc.gather_dtype is None
+    # off (the default): bitwise the chain of the ops as they were, and a module without the
+    # attribute (one saved before it existed)
+    base = _fwd_bwd(enc, call, x, w)
+    parent = _fwd_bwd(enc, lambda e, t: chain(e, t, None), x, w)
+    bare = copy.deepcopy(enc)
+    del bare.gather_dtype
+    assert not hasattr(bare, "gather_dtype")
+    old = _fwd_bwd(bare, call, x, w)
+    for a, b, c in zip(base, parent, old):
+        assert torch.equal(a, b) and torch.equal(a, c)
+    # on: bitwise the chain with the copy handed on; fp32, non-zero parameter gradients
+    enc.gather_dtype = BF16
+    on = _fwd_bwd(enc, call, x, w)
+    ref = _fwd_bwd(enc, lambda e, t: chain(e, t, BF16), x, w)
+    assert len(on) == 2 + 2 * n_layers
+    for a, b in zip(on, ref):
+        assert a.dtype == F32 and torch.equal(a, b)
+    for g in on[1:]:
+        assert bool(g.abs().sum() > 0)
+    assert not torch.equal(on[0], base[0])  # it is another path than the fp32 one
