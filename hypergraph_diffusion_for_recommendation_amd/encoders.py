@@ -328,10 +328,13 @@ def _self_attend(block, x):
     return block(x.unsqueeze(1)).squeeze(1)
 
 
-def _hgcn_ln_res_stack(inc, x, lns, slope, res, attend=None, gather_dtype=None):
+def _hgcn_ln_res_stack(incs, x, lns, slope, res, attend=None, gather_dtype=None,
+                       hop=two_hop_fused):
     """``lns[k](HGCNConv(A, x)) + res`` per layer, no activation on the last (HGNN_cp.py:403-406,
     :428-433): one fused two-hop per layer whose store applies the LeakyReLU, the LayerNorm
-    and the residual; ``attend[k]`` (the UGformer blocks) first when given.
+    and the residual; ``attend[k]`` (the UGformer blocks) first when given. ``incs`` is the
+    tuple of structures ``hop`` takes before ``x``: ``(inc,)`` for two_hop_fused, ``(att, inc)``
+    for att_two_hop_fused (KHGRec's AttHGCNConv stack).
 
     ``gather_dtype`` (the module's attribute; None or torch.bfloat16): the hops gather bfloat16
     tables (functional.two_hop_fused). Every layer but the last then also returns the bf16 copy
@@ -350,16 +353,12 @@ def _hgcn_ln_res_stack(inc, x, lns, slope, res, attend=None, gather_dtype=None):
     for k in range(L):
         if attend is not None:
             x, x16 = _self_attend(attend[k], x), None
-        if gather_dtype is None:
-            x = two_hop_fused(inc, x, epilogue=None if k == L - 1 else "leaky_relu", slope=slope,
-                              norm=lns[k], res1=ress[k], res1_scale=1.0)
-        elif k == L - 1:
-            x = two_hop_fused(inc, x, epilogue=None, slope=slope, norm=lns[k], res1=ress[k],
-                              res1_scale=1.0, gather_dtype=gather_dtype, x16=x16)
-        else:
-            x, x16 = two_hop_fused(inc, x, epilogue="leaky_relu", slope=slope, norm=lns[k],
-                                   res1=ress[k], res1_scale=1.0, gather_dtype=gather_dtype,
-                                   x16=x16, return_x16=True)
+        last = k == L - 1
+        return_x16 = gather_dtype is not None and not last
+        y = hop(*incs, x, epilogue=None if last else "leaky_relu", slope=slope, norm=lns[k],
+                res1=ress[k], res1_scale=1.0, gather_dtype=gather_dtype, x16=x16,
+                return_x16=return_x16)
+        x, x16 = y if return_x16 else (y, None)
     return x
 
 
@@ -400,7 +399,7 @@ class SelfAwareEncoder(nn.Module):
     def forward(self, ego_embeddings, sparse_norm_adj):
         inc = incidence_of(sparse_norm_adj)
         attend = self.ugformer_layers if self.use_self_att else None
-        ego_embeddings = _hgcn_ln_res_stack(inc, ego_embeddings, list(self.lns), self.leaky,
+        ego_embeddings = _hgcn_ln_res_stack((inc,), ego_embeddings, list(self.lns), self.leaky,
                                             ego_embeddings, attend,
                                             getattr(self, "gather_dtype", None))
         nu = self.data.n_users
@@ -427,7 +426,7 @@ class RelationalAwareEncoder(nn.Module):
             self.lns.append(LayerNorm(hyper_dim))
 
     def forward(self, embs, sparse_adj, att_adj=None):
-        return _hgcn_ln_res_stack(incidence_of(sparse_adj), embs, list(self.lns),
+        return _hgcn_ln_res_stack((incidence_of(sparse_adj),), embs, list(self.lns),
                                   float(self.leaky), embs,
                                   gather_dtype=getattr(self, "gather_dtype", None))
 
@@ -456,26 +455,9 @@ class KHGRecRelationalAwareEncoder(nn.Module):
     def forward(self, embs, sparse_adj, att_adj):
         inc = incidence_of(sparse_adj)
         att = incidence_of(att_adj, cache=False)
-        L = self.n_layers
-        uses = fan(embs, L + 1)  # one n-ary gradient sum of the residual (_hgcn_ln_res_stack)
-        x, res = uses[0], uses[1:]
-        gather_dtype = getattr(self, "gather_dtype", None)
-        x16 = None  # the bf16 copy of x a layer's store hands to the next (gather_dtype set)
-        for k in range(L):
-            if gather_dtype is None:
-                x = att_two_hop_fused(att, inc, x, epilogue=None if k == L - 1 else "leaky_relu",
-                                      slope=float(self.leaky), norm=self.lns[k], res1=res[k],
-                                      res1_scale=1.0)
-            elif k == L - 1:
-                x = att_two_hop_fused(att, inc, x, epilogue=None, slope=float(self.leaky),
-                                      norm=self.lns[k], res1=res[k], res1_scale=1.0,
-                                      gather_dtype=gather_dtype, x16=x16)
-            else:
-                x, x16 = att_two_hop_fused(att, inc, x, epilogue="leaky_relu",
-                                           slope=float(self.leaky), norm=self.lns[k],
-                                           res1=res[k], res1_scale=1.0,
-                                           gather_dtype=gather_dtype, x16=x16, return_x16=True)
-        return x
+        return _hgcn_ln_res_stack((att, inc), embs, list(self.lns), float(self.leaky), embs,
+                                  gather_dtype=getattr(self, "gather_dtype", None),
+                                  hop=att_two_hop_fused)
 
 
 class SelfAwareEncoderHD(nn.Module):

@@ -67,6 +67,31 @@ def _epilogue_apply(z: torch.Tensor, epi: int, slope: float):
     return y
 
 
+def _act_hop(ctx, csr, X, val, row_scale, epi: int, slope: float, out_dtype):
+    """The last hop of an operator without the row epilogue, with its activation: fused into
+    the hop's store when the sign test on the output is equivalent to the one on the
+    pre-activation (slope >= 0), else applied after it. Saves what :func:`_act_backward`
+    reads."""
+    fuse = epi != nat.EPI_NONE and slope >= 0.0
+    Y = spmm_csr(csr, X, val=val, row_scale=row_scale, epilogue=epi if fuse else 0, slope=slope,
+                 out_dtype=out_dtype)
+    ctx.epi, ctx.slope = epi, slope
+    if epi != nat.EPI_NONE:
+        ctx.save_for_backward(Y)
+        if not fuse:
+            return _epilogue_apply(Y, epi, slope)
+    return Y
+
+
+def _act_backward(ctx, dY: torch.Tensor) -> torch.Tensor:
+    """dZ from dY through the activation of :func:`_act_hop`."""
+    dZ = dY.contiguous()
+    if ctx.epi != nat.EPI_NONE:
+        (ref,) = ctx.saved_tensors
+        dZ = _epilogue_backward(ref, dZ, ctx.epi, ctx.slope)
+    return dZ
+
+
 class _SpMM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, inc: Incidence, transpose: bool, out_dtype=None):
@@ -106,32 +131,16 @@ class _TwoHop(torch.autograd.Function):
         # hop 1 into the columns (hyperedges) of A: M = Q·Aᵀ·(R·X), stored in X's dtype (a bf16
         # table gives a bf16 M: the second hop's gather is halved too)
         M = spmm_csr(inc.csc, X, val=inc.edge_values("csc", R), row_scale=q)
-        # hop 2 back into the rows (vertices): Z = P·A·M, epilogue fused when the sign test on
-        # the output is equivalent to the one on the pre-activation (slope >= 0)
-        p = inc.scale("row", P)
-        fuse = epi != nat.EPI_NONE and slope >= 0.0
-        Y = spmm_csr(inc.csr, M, val=inc.val, row_scale=p, epilogue=epi if fuse else 0,
-                     slope=slope, out_dtype=out_dtype)
-        ref = Y
-        if epi != nat.EPI_NONE and not fuse:
-            ref = Y
-            Y = _epilogue_apply(Y, epi, slope)
+        # hop 2 back into the rows (vertices): Z = P·A·M, and the activation
         ctx.inc = inc
         ctx.scales = (P, Q, R)
-        ctx.epi = epi
-        ctx.slope = slope
-        if epi != nat.EPI_NONE:
-            ctx.save_for_backward(ref)
-        return Y
+        return _act_hop(ctx, inc.csr, M, inc.val, inc.scale("row", P), epi, slope, out_dtype)
 
     @staticmethod
     def backward(ctx, dY):
         inc = ctx.inc
         P, Q, R = ctx.scales
-        dZ = dY.contiguous()
-        if ctx.epi != nat.EPI_NONE:
-            (ref,) = ctx.saved_tensors
-            dZ = _epilogue_backward(ref, dZ, ctx.epi, ctx.slope)
+        dZ = _act_backward(ctx, dY)
         q = inc.scale("col", Q)
         # dM in the dtype M had (X's), dX in X's
         dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q,
@@ -183,12 +192,13 @@ def _ln_supported16(d: int) -> bool:
 
 
 def _row_epilogue_cfg(what: str, n_rows: int, d: int, epilogue, slope, norm, out_scale, res1,
-                      res1_scale, res2, res2_scale):
+                      res1_scale, res2, res2_scale, gather16: bool = False):
     """Checks the epilogue's arguments for the operator ``what`` over [n_rows, d] rows (the
     LayerNorm's and the residuals' shapes; an operator that rejects 16-bit tensors does so
     itself, in its own words) and returns ``gamma, beta, cfg, fusable``:
     ``cfg = (epi, slope, ln, eps, out_scale, s1, s2)``, and whether the fused store can hold the
-    row (LayerNorm needs a row in one lane group, an activation slope >= 0)."""
+    row (LayerNorm needs a row in one lane group — of the store over a bfloat16 table with
+    ``gather16`` — and an activation slope >= 0)."""
     epi = _EPI[epilogue]
     ln = norm is not None
     if ln and tuple(norm.normalized_shape) != (d,):
@@ -200,7 +210,8 @@ def _row_epilogue_cfg(what: str, n_rows: int, d: int, epilogue, slope, norm, out
     beta = norm.bias if ln and norm.bias is not None else None
     cfg = (epi, float(slope), ln, float(norm.eps) if ln else 0.0, float(out_scale),
            float(res1_scale), float(res2_scale))
-    fusable = not ((ln and not _ln_supported(d)) or (epi != nat.EPI_NONE and slope < 0))
+    held = _ln_supported16 if gather16 else _ln_supported
+    fusable = not ((ln and not held(d)) or (epi != nat.EPI_NONE and slope < 0))
     return gamma, beta, cfg, fusable
 
 
@@ -286,9 +297,10 @@ def _res_grad(ctx, dY, k, s):
     return dY if s == 1.0 else dY * s
 
 
-def _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale):
+def _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale,
+                          return_x16: bool = False):
     """The epilogue after its activation as separate device ops, for rows the fused store
-    cannot hold."""
+    cannot hold; with ``return_x16`` also the result's detached bfloat16 copy."""
     if norm is not None:
         y = norm(y)
     y = out_scale * y
@@ -296,26 +308,53 @@ def _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale
         y = y + res1_scale * res1
     if res2 is not None:
         y = y + res2_scale * res2
-    return y
+    return (y, y.detach().bfloat16()) if return_x16 else y
+
+
+def _table16(X: torch.Tensor, x16) -> torch.Tensor:
+    """The bfloat16 table a fused operator's first hop gathers with ``gather_dtype`` set: the
+    caller's ``x16`` when there is one, else bf16(X)."""
+    return x16.contiguous() if x16 is not None else X.contiguous().bfloat16()
+
+
+def _fused_store16(ctx, csr, Z16: torch.Tensor, val, row_scale, ex, return_x16: bool):
+    """The last hop of a fused operator over bfloat16-gathered tables: hgd_spmm_fused_dt reads
+    ``Z16`` and its store runs the row epilogue ``ex`` into a float32 Y; on ``return_x16``
+    ``(Y, Y16)``, the bf16 copy of Y the same store writes, a non-differentiable output."""
+    Y16 = (torch.empty((csr.n_rows, Z16.shape[1]), dtype=torch.bfloat16, device=Z16.device)
+           if return_x16 else None)
+    Y = spmm_csr_fused_dt(csr, Z16, ex, val=val, row_scale=row_scale, out16=Y16)
+    if not return_x16:
+        return Y
+    ctx.mark_non_differentiable(Y16)
+    return Y, Y16
 
 
 class _FusedTwoHop(torch.autograd.Function):
     """``Y = out_scale·LN(epi(P·A·Q·Aᵀ·R·X)) + s1·res1 + s2·res2`` — the second hop's store runs
     the activation, LayerNorm and residual blend (hgd_spmm_fused); the backward runs their
-    gradient in one pass (hgd_row_epilogue_backward) before the two backward hops."""
+    gradient in one pass (hgd_row_epilogue_backward) before the two backward hops.
+
+    ``gather16`` (the caller's ``gather_dtype``): both hops gather bfloat16 tables — bf16(X) or
+    the caller's ``x16``, and the intermediate M stored in bf16 (as :func:`two_hop` stores it
+    for a bf16 X) — into a float32 Y (:func:`_fused_store16`). Backward: the epilogue's gradient
+    in fp32 as without it, then dM stored in bf16 and dX in fp32."""
 
     @staticmethod
-    def forward(ctx, X, gamma, beta, res1, res2, inc: Incidence, scales, cfg):
+    def forward(ctx, X, gamma, beta, res1, res2, inc: Incidence, scales, cfg, gather16: bool,
+                x16, return_x16: bool):
         P, Q, R = scales
-        X = X.contiguous()
-        M = spmm_csr(inc.csc, X, val=inc.edge_values("csc", R), row_scale=inc.scale("col", Q))
+        M = spmm_csr(inc.csc, _table16(X, x16) if gather16 else X.contiguous(),
+                     val=inc.edge_values("csc", R), row_scale=inc.scale("col", Q))
         ex = _row_epilogue_setup(ctx, inc.n_rows, X.shape[1], X.device, gamma, beta, res1, res2,
                                  cfg)
-        ctx.inc, ctx.scales = inc, scales
+        ctx.inc, ctx.scales, ctx.gather16 = inc, scales, gather16
+        if gather16:
+            return _fused_store16(ctx, inc.csr, M, inc.val, inc.scale("row", P), ex(), return_x16)
         return spmm_csr(inc.csr, M, val=inc.val, row_scale=inc.scale("row", P), ex=ex())
 
     @staticmethod
-    def backward(ctx, dY):
+    def backward(ctx, dY, _dY16=None):
         inc = ctx.inc
         P, Q, R = ctx.scales
         need_dx = ctx.needs_input_grad[0]
@@ -329,9 +368,12 @@ class _FusedTwoHop(torch.autograd.Function):
                 # first backward hop (n_cols multiplies instead of an [n, d] pass)
                 q = (torch.full((inc.n_cols,), dz_scale, dtype=torch.float32, device=dZ.device)
                      if q is None else q * dz_scale)
-            dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q)
-            dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=inc.scale("row", R))
-        return dX, dgamma, dbeta, dres1, dres2, None, None, None
+            g16 = ctx.gather16
+            dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q,
+                          out_dtype=torch.bfloat16 if g16 else None)
+            dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=inc.scale("row", R),
+                          out_dtype=torch.float32 if g16 else None)
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None, None
 
 
 def _gather16(what: str, gather_dtype, X: torch.Tensor, x16, return_x16: bool) -> bool:
@@ -352,50 +394,6 @@ def _gather16(what: str, gather_dtype, X: torch.Tensor, x16, return_x16: bool) -
             raise ValueError(f"{what}: x16 {tuple(x16.shape)} on {x16.device} is no copy of X "
                              f"{tuple(X.shape)} on {X.device}")
     return True
-
-
-class _FusedTwoHop16(torch.autograd.Function):
-    """:class:`_FusedTwoHop` gathering bfloat16 tables: X16 = bf16(X) (or the caller's copy), the
-    intermediate M stored in bf16 (as :func:`two_hop` stores it for a bf16 X), and the second
-    hop's fused store reading it (hgd_spmm_fused_dt) into a float32 Y, with the bf16 copy of Y
-    as a second, non-differentiable output on request. Backward: the epilogue's gradient in
-    fp32 as before, then dM stored in bf16 and dX in fp32."""
-
-    @staticmethod
-    def forward(ctx, X, gamma, beta, res1, res2, inc: Incidence, scales, cfg, x16,
-                return_x16: bool):
-        P, Q, R = scales
-        X16 = x16.contiguous() if x16 is not None else X.contiguous().bfloat16()
-        M16 = spmm_csr(inc.csc, X16, val=inc.edge_values("csc", R), row_scale=inc.scale("col", Q))
-        n, d = inc.n_rows, X.shape[1]
-        ex = _row_epilogue_setup(ctx, n, d, X.device, gamma, beta, res1, res2, cfg)
-        ctx.inc, ctx.scales = inc, scales
-        Y16 = torch.empty((n, d), dtype=torch.bfloat16, device=X.device) if return_x16 else None
-        Y = spmm_csr_fused_dt(inc.csr, M16, ex(), val=inc.val, row_scale=inc.scale("row", P),
-                              out16=Y16)
-        if not return_x16:
-            return Y
-        ctx.mark_non_differentiable(Y16)
-        return Y, Y16
-
-    @staticmethod
-    def backward(ctx, dY, _dY16=None):
-        inc = ctx.inc
-        P, Q, R = ctx.scales
-        need_dx = ctx.needs_input_grad[0]
-        dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
-            ctx, dY.contiguous(), need_dx)
-        dX = None
-        if need_dx:
-            q = inc.scale("col", Q)
-            if dz_scale != 1.0:  # a pure blend (see _FusedTwoHop.backward)
-                q = (torch.full((inc.n_cols,), dz_scale, dtype=torch.float32, device=dZ.device)
-                     if q is None else q * dz_scale)
-            dM16 = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q,
-                            out_dtype=torch.bfloat16)
-            dX = spmm_csr(inc.csr, dM16, val=inc.val, row_scale=inc.scale("row", R),
-                          out_dtype=torch.float32)
-        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None
 
 
 def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
@@ -429,19 +427,17 @@ def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
                             f"form), got {t.dtype}; use two_hop for a bfloat16 table")
     gamma, beta, cfg, fusable = _row_epilogue_cfg(
         "two_hop_fused", inc.n_rows, X.shape[1], epilogue, slope, norm, out_scale, res1,
-        res1_scale, res2, res2_scale)
+        res1_scale, res2, res2_scale, gather16)
+    if fusable:
+        return _FusedTwoHop.apply(X, gamma, beta, res1, res2, inc, (P, Q, R), cfg, gather16, x16,
+                                  bool(return_x16))
     if gather16:
-        if fusable and not (norm is not None and not _ln_supported16(X.shape[1])):
-            return _FusedTwoHop16.apply(X, gamma, beta, res1, res2, inc, (P, Q, R), cfg, x16,
-                                        bool(return_x16))
         y = two_hop(inc, X.bfloat16(), P=P, Q=Q, R=R, epilogue=epilogue, slope=slope,
                     out_dtype=torch.float32)
-        y = _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
-        return (y, y.detach().bfloat16()) if return_x16 else y
-    if not fusable:
+    else:
         y = two_hop(inc, X, P=P, Q=Q, R=R, epilogue=epilogue, slope=slope)
-        return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
-    return _FusedTwoHop.apply(X, gamma, beta, res1, res2, inc, (P, Q, R), cfg)
+    return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale,
+                                 return_x16)
 
 
 def _att_hops(att: Incidence, inc: Incidence, X: torch.Tensor, store=None):
@@ -461,32 +457,34 @@ def _check_att(att: Incidence, inc: Incidence, X: torch.Tensor, what: str) -> No
         raise ValueError(f"{what}: X {tuple(X.shape)} for an att of {att.shape}")
 
 
+def _att_grad(att: Incidence, inc: Incidence, dZ: torch.Tensor, store16: bool) -> torch.Tensor:
+    """``dX = att·K·Kᵀ·attᵀ·dZ``: the operator is symmetric, so the backward is its four hops
+    over dZ. ``store16``: the first three store bfloat16, the last one writes float32."""
+    if store16:
+        return spmm_csr(att.csr, _att_hops(att, inc, dZ, store=torch.bfloat16), val=att.val,
+                        out_dtype=torch.float32)
+    return spmm_csr(att.csr, _att_hops(att, inc, dZ), val=att.val)
+
+
 class _AttTwoHop(torch.autograd.Function):
-    """``Y = epi(att·K·Kᵀ·attᵀ·X)`` as four hops, the activation in the last hop's store. The
-    operator is symmetric, so the backward is the same four hops over ``epi'(dY)``. Gradient
-    through ``X`` only: the attention carries none (KHGRec.py:331 assigns ``.data``)."""
+    """``Y = epi(att·K·Kᵀ·attᵀ·X)`` as four hops, the activation in the last hop's store; the
+    backward is the same four hops over ``epi'(dY)``. Gradient through ``X`` only: the attention
+    carries none (KHGRec.py:331 assigns ``.data``). ``store16`` (a caller's ``gather_dtype``, for
+    the rows the fused store cannot hold): the float32 ``X`` is gathered as bf16(X) and T, M
+    and Z are stored in bfloat16 in both directions; the last hop writes float32."""
 
     @staticmethod
-    def forward(ctx, X, att: Incidence, inc: Incidence, epi: int, slope: float):
-        Z = _att_hops(att, inc, X.contiguous())
-        fuse = epi != nat.EPI_NONE and slope >= 0.0
-        Y = spmm_csr(att.csr, Z, val=att.val, epilogue=epi if fuse else 0, slope=slope)
-        ref = Y
-        if epi != nat.EPI_NONE and not fuse:
-            Y = _epilogue_apply(ref, epi, slope)
-        ctx.att, ctx.inc, ctx.epi, ctx.slope = att, inc, epi, slope
-        if epi != nat.EPI_NONE:
-            ctx.save_for_backward(ref)
-        return Y
+    def forward(ctx, X, att: Incidence, inc: Incidence, epi: int, slope: float, store16: bool):
+        X = X.contiguous()
+        Z = _att_hops(att, inc, X.bfloat16() if store16 else X)
+        ctx.att, ctx.inc, ctx.store16 = att, inc, store16
+        return _act_hop(ctx, att.csr, Z, att.val, None, epi, slope,
+                        torch.float32 if store16 else None)
 
     @staticmethod
     def backward(ctx, dY):
-        dZ = dY.contiguous()
-        if ctx.epi != nat.EPI_NONE:
-            (ref,) = ctx.saved_tensors
-            dZ = _epilogue_backward(ref, dZ, ctx.epi, ctx.slope)
-        dX = spmm_csr(ctx.att.csr, _att_hops(ctx.att, ctx.inc, dZ), val=ctx.att.val)
-        return dX, None, None, None, None
+        dX = _att_grad(ctx.att, ctx.inc, _act_backward(ctx, dY), ctx.store16)
+        return dX, None, None, None, None, None
 
 
 def att_two_hop(att: Incidence, inc: Incidence, X: torch.Tensor, epilogue: Optional[str] = None,
@@ -496,89 +494,29 @@ def att_two_hop(att: Incidence, inc: Incidence, X: torch.Tensor, epilogue: Optio
     ``att`` [n, m] and ``inc`` = K [m, c] are Incidences (``inc`` may be an edge-dropped view);
     ``X`` is float32 [n, d]. Autograd through ``X`` only."""
     _check_att(att, inc, X, "att_two_hop")
-    return _AttTwoHop.apply(X, att, inc, _EPI[epilogue], float(slope))
+    return _AttTwoHop.apply(X, att, inc, _EPI[epilogue], float(slope), False)
 
 
 class _FusedAttTwoHop(torch.autograd.Function):
     """``Y = out_scale·LN(epi(att·K·Kᵀ·attᵀ·X)) + s1·res1 + s2·res2`` — :class:`_FusedTwoHop`
     over the four hops of :func:`att_two_hop`: the last hop's store runs the activation,
-    LayerNorm and residual blend, the backward their gradient in one pass before four hops."""
+    LayerNorm and residual blend, the backward their gradient in one pass before four hops.
+    ``gather16``, ``x16`` and ``return_x16`` as there: bf16(X), T, M and Z are stored in
+    bfloat16 in both directions, Y and dX are float32."""
 
     @staticmethod
-    def forward(ctx, X, gamma, beta, res1, res2, att: Incidence, inc: Incidence, cfg):
-        Z = _att_hops(att, inc, X.contiguous())
+    def forward(ctx, X, gamma, beta, res1, res2, att: Incidence, inc: Incidence, cfg,
+                gather16: bool, x16, return_x16: bool):
+        Z = _att_hops(att, inc, _table16(X, x16) if gather16 else X.contiguous())
         ex = _row_epilogue_setup(ctx, att.n_rows, X.shape[1], X.device, gamma, beta, res1, res2,
                                  cfg)
-        ctx.att, ctx.inc = att, inc
+        ctx.att, ctx.inc, ctx.gather16 = att, inc, gather16
+        if gather16:
+            return _fused_store16(ctx, att.csr, Z, att.val, None, ex(), return_x16)
         return spmm_csr(att.csr, Z, val=att.val, ex=ex())
 
     @staticmethod
-    def backward(ctx, dY):
-        att = ctx.att
-        need_dx = ctx.needs_input_grad[0]
-        dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
-            ctx, dY.contiguous(), need_dx)
-        dX = None
-        if need_dx:
-            if dz_scale != 1.0:  # a pure blend
-                dZ = dZ * dz_scale
-            dX = spmm_csr(att.csr, _att_hops(att, ctx.inc, dZ), val=att.val)
-        return dX, dgamma, dbeta, dres1, dres2, None, None, None
-
-
-class _AttTwoHop16(torch.autograd.Function):
-    """:class:`_AttTwoHop` over a float32 ``X`` gathering bfloat16 tables (bf16(X), T, M and Z
-    stored in bf16; the last hop writes float32), for the rows the fused store cannot hold."""
-
-    @staticmethod
-    def forward(ctx, X, att: Incidence, inc: Incidence, epi: int, slope: float):
-        Z = _att_hops(att, inc, X.contiguous().bfloat16())
-        fuse = epi != nat.EPI_NONE and slope >= 0.0
-        Y = spmm_csr(att.csr, Z, val=att.val, epilogue=epi if fuse else 0, slope=slope,
-                     out_dtype=torch.float32)
-        ref = Y
-        if epi != nat.EPI_NONE and not fuse:
-            Y = _epilogue_apply(ref, epi, slope)
-        ctx.att, ctx.inc, ctx.epi, ctx.slope = att, inc, epi, slope
-        if epi != nat.EPI_NONE:
-            ctx.save_for_backward(ref)
-        return Y
-
-    @staticmethod
-    def backward(ctx, dY):
-        dZ = dY.contiguous()
-        if ctx.epi != nat.EPI_NONE:
-            (ref,) = ctx.saved_tensors
-            dZ = _epilogue_backward(ref, dZ, ctx.epi, ctx.slope)
-        dX = spmm_csr(ctx.att.csr, _att_hops(ctx.att, ctx.inc, dZ, store=torch.bfloat16),
-                      val=ctx.att.val, out_dtype=torch.float32)
-        return dX, None, None, None, None
-
-
-class _FusedAttTwoHop16(torch.autograd.Function):
-    """:class:`_FusedAttTwoHop` gathering bfloat16 tables: bf16(X) (or the caller's copy), T, M
-    and Z stored in bf16, and the last hop's fused store reading Z (hgd_spmm_fused_dt) into a
-    float32 Y, with its bf16 copy as a second, non-differentiable output on request. Backward:
-    the epilogue's gradient in fp32, three hops stored in bf16 and dX in fp32."""
-
-    @staticmethod
-    def forward(ctx, X, gamma, beta, res1, res2, att: Incidence, inc: Incidence, cfg, x16,
-                return_x16: bool):
-        X16 = x16.contiguous() if x16 is not None else X.contiguous().bfloat16()
-        Z16 = _att_hops(att, inc, X16)
-        n, d = att.n_rows, X.shape[1]
-        ex = _row_epilogue_setup(ctx, n, d, X.device, gamma, beta, res1, res2, cfg)
-        ctx.att, ctx.inc = att, inc
-        Y16 = torch.empty((n, d), dtype=torch.bfloat16, device=X.device) if return_x16 else None
-        Y = spmm_csr_fused_dt(att.csr, Z16, ex(), val=att.val, out16=Y16)
-        if not return_x16:
-            return Y
-        ctx.mark_non_differentiable(Y16)
-        return Y, Y16
-
-    @staticmethod
     def backward(ctx, dY, _dY16=None):
-        att = ctx.att
         need_dx = ctx.needs_input_grad[0]
         dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
             ctx, dY.contiguous(), need_dx)
@@ -586,9 +524,8 @@ class _FusedAttTwoHop16(torch.autograd.Function):
         if need_dx:
             if dz_scale != 1.0:  # a pure blend
                 dZ = dZ * dz_scale
-            dX = spmm_csr(att.csr, _att_hops(att, ctx.inc, dZ, store=torch.bfloat16),
-                          val=att.val, out_dtype=torch.float32)
-        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None
+            dX = _att_grad(ctx.att, ctx.inc, dZ, ctx.gather16)
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None, None
 
 
 def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
@@ -619,18 +556,13 @@ def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
             raise TypeError(f"att_two_hop_fused: float32 only, got {t.dtype}")
     gamma, beta, cfg, fusable = _row_epilogue_cfg(
         "att_two_hop_fused", att.n_rows, X.shape[1], epilogue, slope, norm, out_scale, res1,
-        res1_scale, res2, res2_scale)
-    if gather16:
-        if fusable and not (norm is not None and not _ln_supported16(X.shape[1])):
-            return _FusedAttTwoHop16.apply(X, gamma, beta, res1, res2, att, inc, cfg, x16,
-                                           bool(return_x16))
-        y = _AttTwoHop16.apply(X, att, inc, _EPI[epilogue], float(slope))
-        y = _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
-        return (y, y.detach().bfloat16()) if return_x16 else y
-    if not fusable:
-        y = att_two_hop(att, inc, X, epilogue=epilogue, slope=slope)
-        return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale)
-    return _FusedAttTwoHop.apply(X, gamma, beta, res1, res2, att, inc, cfg)
+        res1_scale, res2, res2_scale, gather16)
+    if fusable:
+        return _FusedAttTwoHop.apply(X, gamma, beta, res1, res2, att, inc, cfg, gather16, x16,
+                                     bool(return_x16))
+    y = _AttTwoHop.apply(X, att, inc, _EPI[epilogue], float(slope), gather16)
+    return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale,
+                                 return_x16)
 
 
 def _linear_native_ok(X: torch.Tensor, weight: torch.Tensor) -> bool:

@@ -465,12 +465,19 @@ def spmm_block_order(csr: CSR, d: int, blocks: int) -> bool:
 _HOP_DTYPES = {torch.float32: nat.DT_F32, torch.bfloat16: nat.DT_BF16}
 
 
+def _hop_names(fused16: bool) -> Tuple[str, str]:
+    """Who rejects a call that reached :func:`spmm_csr`'s checks and what it calls its table:
+    :func:`spmm_csr_fused_dt` and ``X16`` when the call came through that function."""
+    return ("spmm_fused_dt", "X16") if fused16 else ("spmm", "X")
+
+
 def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
              row_scale: Optional[torch.Tensor] = None, epilogue: int = nat.EPI_NONE,
              slope: float = 0.0, out: Optional[torch.Tensor] = None,
              row_begin: int = 0, row_end: Optional[int] = None,
              ex: Optional[nat.RowEpilogue] = None, blocks: Optional[int] = None,
-             out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+             out_dtype: Optional[torch.dtype] = None, _fused16: bool = False,
+             _out16: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``Y[r] = epi(row_scale[r] * Σ_e val[e] * X[col[e]])`` for r in [row_begin, row_end).
 
     ``X`` is float32 or bfloat16; the result is ``out.dtype`` if ``out`` is given, else
@@ -486,22 +493,28 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     ``blocks``: None = :func:`spmm_blocks` decides whether the hop runs source-blocked
     (hgd_spmm_blocked) and, for an fp32 hop over a structure with split rows,
     :func:`spmm_blocks_split` whether it runs as hgd_spmm_blocked_split; 0 = never (e.g. into
-    uncached exchange memory, which the blocked hop would read back P−1 times)."""
+    uncached exchange memory, which the blocked hop would read back P−1 times).
+
+    ``_fused16`` / ``_out16`` are :func:`spmm_csr_fused_dt`'s, which runs this body after its
+    own checks: the one 16-bit hop that takes ``ex``, and its bf16 copy of the result. A
+    rejection then speaks in that function's words (:func:`_hop_names`)."""
     if X.dim() != 2:
-        raise ValueError(f"spmm: X must be 2-D, got {tuple(X.shape)}")
+        raise ValueError("%s: %s must be 2-D, got %s" % (*_hop_names(_fused16), tuple(X.shape)))
     if X.dtype not in _HOP_DTYPES:
         raise TypeError(f"spmm: X must be float32 or bfloat16, got {X.dtype}")
     y_dtype = out.dtype if out is not None else (out_dtype or X.dtype)
     if y_dtype not in _HOP_DTYPES:
         raise TypeError(f"spmm: the output must be float32 or bfloat16, got {y_dtype}")
     dt = X.dtype != torch.float32 or y_dtype != torch.float32  # a 16-bit side: the _dt entries
-    if dt and ex is not None:
+    if dt and ex is not None and not _fused16:
         raise TypeError("spmm: the fused row epilogue (ex=) is float32-only; a bfloat16 "
                         f"table or output cannot take it (X {X.dtype}, output {y_dtype})")
     if X.device.type != "cuda":
-        raise RuntimeError("spmm: X must be a device (cuda/hip) tensor; there is no CPU path")
+        raise RuntimeError("%s: %s must be a device (cuda/hip) tensor; there is no CPU path"
+                           % _hop_names(_fused16))
     if X.shape[0] != csr.n_cols:
-        raise ValueError(f"spmm: X has {X.shape[0]} rows, structure expects {csr.n_cols}")
+        raise ValueError("%s: %s has %d rows, structure expects %d"
+                         % (*_hop_names(_fused16), X.shape[0], csr.n_cols))
     if X.stride(1) != 1:
         X = X.contiguous()
     d = X.shape[1]
@@ -512,9 +525,9 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     if d == 0 or row_end <= row_begin:
         return out
     if val is not None and val.numel() != csr.nnz:
-        raise ValueError("spmm: val size mismatch")
+        raise ValueError(f"{_hop_names(_fused16)[0]}: val size mismatch")
     if row_scale is not None and row_scale.numel() != csr.n_rows:
-        raise ValueError("spmm: row_scale size mismatch")
+        raise ValueError(f"{_hop_names(_fused16)[0]}: row_scale size mismatch")
     lib = nat.load()
     plan_ptr = ctypes.byref(csr.plan)
     # the plan is immutable once built: its workspace size per width is asked for once
@@ -556,6 +569,16 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
             nat.ptr(csr.ordered_scale(row_scale)), n, m, rb, re_, xp, ldx, yp, ldy, d,
             int(epilogue), float(slope), plan_ptr, wp, wsb, order.data_ptr(), st),
             "hgd_spmm_ordered")
+    elif _fused16:  # (ex: never blocked; a bf16 table: never row-ordered)
+        y16p, ld16 = nat.ptr(_out16), 0 if _out16 is None else _out16.stride(0)
+        if mask is not None:
+            nat.check(lib.hgd_spmm_masked_fused_dt(
+                rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, nat.DT_BF16, ldx, yp, ldy, d,
+                ctypes.byref(ex), y16p, ld16, plan_ptr, wp, wsb, st), "hgd_spmm_masked_fused_dt")
+        else:
+            nat.check(lib.hgd_spmm_fused_dt(
+                rp, cp, vp, sp, n, m, rb, re_, xp, nat.DT_BF16, ldx, yp, ldy, d,
+                ctypes.byref(ex), y16p, ld16, plan_ptr, wp, wsb, st), "hgd_spmm_fused_dt")
     elif dt and mask is not None:
         nat.check(lib.hgd_spmm_masked_dt(
             rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, _HOP_DTYPES[X.dtype], ldx, yp,
@@ -649,8 +672,6 @@ def spmm_csr_fused_dt(csr: CSR, X16: torch.Tensor, ex: nat.RowEpilogue,
     ``out16`` (bfloat16 [n_rows, d]) is filled with the rows of Y rounded to nearest even, from
     the registers Y was stored from: the table a following hop gathers. Never source-blocked and
     never walked in a row order, like the fp32 fused hop."""
-    if X16.dim() != 2:
-        raise ValueError(f"spmm_fused_dt: X16 must be 2-D, got {tuple(X16.shape)}")
     if X16.dtype != torch.bfloat16:
         raise TypeError(f"spmm_fused_dt: X16 must be bfloat16, got {X16.dtype}")
     if out is not None and out.dtype != torch.float32:
@@ -659,65 +680,16 @@ def spmm_csr_fused_dt(csr: CSR, X16: torch.Tensor, ex: nat.RowEpilogue,
         raise TypeError(f"spmm_fused_dt: out16 must be bfloat16, got {out16.dtype}")
     if ex is None:
         raise ValueError("spmm_fused_dt: needs a row epilogue (ex)")
-    if X16.device.type != "cuda":
-        raise RuntimeError("spmm_fused_dt: X16 must be a device (cuda/hip) tensor; there is no "
-                           "CPU path")
-    if X16.shape[0] != csr.n_cols:
-        raise ValueError(f"spmm_fused_dt: X16 has {X16.shape[0]} rows, structure expects "
-                         f"{csr.n_cols}")
-    if X16.stride(1) != 1:
-        X16 = X16.contiguous()
-    d = X16.shape[1]
-    if out is None:
-        out = torch.empty((csr.n_rows, d), dtype=torch.float32, device=X16.device)
-    for name, t in (("out", out), ("out16", out16)):
-        if t is not None and (tuple(t.shape) != (csr.n_rows, d) or t.stride(1) != 1
-                              or t.device != X16.device):
-            raise ValueError(f"spmm_fused_dt: {name} must be a [{csr.n_rows}, {d}] matrix with "
-                             f"unit column stride on {X16.device}")
-    if row_end is None:
-        row_end = csr.n_rows
-    if d == 0 or row_end <= row_begin:
-        return out
-    if val is not None and val.numel() != csr.nnz:
-        raise ValueError("spmm_fused_dt: val size mismatch")
-    if row_scale is not None and row_scale.numel() != csr.n_rows:
-        raise ValueError("spmm_fused_dt: row_scale size mismatch")
-    lib = nat.load()
-    plan_ptr = ctypes.byref(csr.plan)
-    wsb = csr._ws_bytes.get(d)
-    if wsb is None:
-        wsb = csr._ws_bytes[d] = lib.hgd_spmm_workspace_size(plan_ptr, d)
-    ws = _ws(wsb, X16.device) if wsb else None
-    timer = profiling.active()
-    if timer is not None:
-        t0 = timer.begin()
-    mask = getattr(csr, "mask", None)
-    rp, cp, vp = csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None, nat.ptr(val)
-    sp, n, m, rb, re_ = nat.ptr(row_scale), csr.n_rows, csr.n_cols, int(row_begin), int(row_end)
-    xp, ldx, yp, ldy = X16.data_ptr(), X16.stride(0), out.data_ptr(), out.stride(0)
-    y16p, ld16 = nat.ptr(out16), 0 if out16 is None else out16.stride(0)
-    wp, st = nat.ptr(ws), _stream(X16.device)
-    if mask is not None:
-        nat.check(lib.hgd_spmm_masked_fused_dt(
-            rp, cp, vp, mask.data_ptr() if csr.nnz else None, float(csr.keep), sp, n, m, rb, re_,
-            xp, nat.DT_BF16, ldx, yp, ldy, d, ctypes.byref(ex), y16p, ld16, plan_ptr, wp, wsb,
-            st), "hgd_spmm_masked_fused_dt")
-    else:
-        nat.check(lib.hgd_spmm_fused_dt(
-            rp, cp, vp, sp, n, m, rb, re_, xp, nat.DT_BF16, ldx, yp, ldy, d, ctypes.byref(ex),
-            y16p, ld16, plan_ptr, wp, wsb, st), "hgd_spmm_fused_dt")
-    if timer is not None:
-        full = rb == 0 and re_ == csr.n_rows
-
-        def nbytes(csr=csr, rb=rb, re_=re_, full=full, d=d, hv=val is not None,
-                   hs=row_scale is not None):
-            nnz = csr.nnz if full else int(csr.rowptr[re_].item() - csr.rowptr[rb].item())
-            return (profiling.hop_bytes(nnz, re_ - rb, d, x_bytes=2, y_bytes=4),
-                    profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, 0, x_bytes=2, y_bytes=4))
-
-        timer.end(t0, nbytes)
-    return out
+    if X16.dim() == 2:  # (any other is the shared checks' to reject)
+        shape = (csr.n_rows, X16.shape[1])
+        for name, t in (("out", out), ("out16", out16)):
+            if t is not None and (tuple(t.shape) != shape or t.stride(1) != 1
+                                  or t.device != X16.device):
+                raise ValueError(f"spmm_fused_dt: {name} must be a [{shape[0]}, {shape[1]}] "
+                                 f"matrix with unit column stride on {X16.device}")
+    # the shared checks, the plan's workspace, the launch and the timer's record are spmm_csr's
+    return spmm_csr(csr, X16, val, row_scale, nat.EPI_NONE, 0.0, out, row_begin, row_end, ex, 0,
+                    torch.float32, True, out16)
 
 
 class Incidence:

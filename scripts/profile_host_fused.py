@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Host (Python) issue time of one layer's forward + backward for two_hop_fused, att_two_hop_fused
-and hgconv2 on a graph so small (700 x 450, 6,000 nonzeros, d = 64) that the device never limits
-the loop: the minimum over 7 repeats of 1000 unsynchronised steps, one line per operator. It
+(each also with gather_dtype=torch.bfloat16) and hgconv2 on a graph so small (700 x 450, 6,000
+nonzeros, d = 64) that the device never limits the loop: the minimum over 7 repeats of 1000 unsynchronised steps, one line per operator. It
 resolves a few microseconds of Python per layer, which profile_host_overhead.py's single timing
 at the ML-1M shape does not."""
 import os
@@ -43,11 +43,24 @@ def att_fused():
     torch.autograd.grad(Y, leaves, dY)
 
 
+def fused16():
+    Y = F.two_hop_fused(inc, X, P="sym", Q="mean", R="sym", epilogue="leaky_relu", slope=0.1,
+                        norm=norm, res1=res, gather_dtype=torch.bfloat16)
+    torch.autograd.grad(Y, leaves, dY)
+
+
+def att_fused16():
+    Y = F.att_two_hop_fused(att, inc, X, epilogue="leaky_relu", slope=0.1, norm=norm, res1=res,
+                            gather_dtype=torch.bfloat16)
+    torch.autograd.grad(Y, leaves, dY)
+
+
 def plain():
     torch.autograd.grad(F.hgconv2(inc, X), X, dY)
 
 
-for name, fn in (("two_hop_fused", fused), ("att_two_hop_fused", att_fused), ("hgconv2", plain)):
+for name, fn in (("two_hop_fused", fused), ("att_two_hop_fused", att_fused), ("hgconv2", plain),
+                 ("two_hop_fused bf16", fused16), ("att_two_hop_fused bf16", att_fused16)):
     for _ in range(200):
         fn()
     torch.cuda.synchronize()

@@ -297,8 +297,12 @@ def _long_row_coo(rng, n_rows, n_cols, nnz, row):
 
 def _partial_operator(op, dev, d, rng):
     """``(n_rows, f)`` with ``f(X, res1, res2, **epilogue keywords) -> Y`` for one of the four
-    operators over the fused row epilogue."""
+    operators over the fused row epilogue; ``<op>-bf16``: that operator (one of the two over
+    hops) with ``gather_dtype=torch.bfloat16``, over the structures and inputs of ``<op>``."""
     from hypergraph_diffusion_for_recommendation_amd import functional as F
+    if op.endswith("-bf16"):
+        n, f = _partial_operator(op[:-len("-bf16")], dev, d, rng)
+        return n, lambda X, **kw: f(X, gather_dtype=torch.bfloat16, **kw)
     if op == "bipartite_hop_fused":
         from hypergraph_diffusion_for_recommendation_amd import sharded as S
         r, c = _long_row_coo(rng, 37, 23, 300, 5)
@@ -318,16 +322,15 @@ def _partial_operator(op, dev, d, rng):
     return 70, lambda X, **kw: F.att_two_hop_fused(att, inc, X, **kw)
 
 
-@pytest.mark.parametrize("d", [20, 64])
-@pytest.mark.parametrize("case", _PARTIAL_CASES, ids=["ln-leaky", "relu", "blend", "blend1"])
-@pytest.mark.parametrize("op", ["two_hop_fused", "att_two_hop_fused", "row_epilogue",
-                                "bipartite_hop_fused"])
-def test_partial_gradients(dev, op, case, d):
-    """The gradients of a subset of (X, γ, β, res1, res2) are bitwise those of the run in which
-    every input requires one, and Y does not depend on who asks: the backward skips what nobody
-    needs (the epilogue's kernel when neither dZ, dγ nor dβ is wanted) and nothing else."""
+_ALL_INPUTS = ("X", "gamma", "beta", "res1", "res2")
+
+
+def _partial_runner(dev, op, case, d):
+    """``run(names, **kw) -> (Y, gradients by name, Y16 or None)`` for one operator and case:
+    only the inputs in ``names`` require a gradient; ``kw`` goes to the operator."""
     act, slope, ln, out_scale = case
-    rng = np.random.default_rng(1000 * d + 10 * _PARTIAL_CASES.index(case) + len(op))
+    base = op[:-len("-bf16")] if op.endswith("-bf16") else op  # (the same inputs either way)
+    rng = np.random.default_rng(1000 * d + 10 * _PARTIAL_CASES.index(case) + len(base))
     n, f = _partial_operator(op, dev, d, rng)
     t = {k: torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
          for k in ("X", "res1", "res2", "dY")}
@@ -338,23 +341,54 @@ def test_partial_gradients(dev, op, case, d):
             norm.weight.copy_(torch.from_numpy(rng.random(d).astype(np.float32) + 0.5))
             norm.bias.copy_(torch.from_numpy(rng.standard_normal(d).astype(np.float32)))
 
-    def run(names):
+    def run(names, **kw):
         leaf = {k: t[k].clone().requires_grad_(k in names) for k in ("X", "res1", "res2")}
         if ln:
             leaf["gamma"] = norm.weight.requires_grad_("gamma" in names)
             leaf["beta"] = norm.bias.requires_grad_("beta" in names)
         Y = f(leaf["X"], res1=leaf["res1"], res2=leaf["res2"], epilogue=act, slope=slope,
-              norm=norm, out_scale=out_scale, res1_scale=1.0, res2_scale=0.3)
+              norm=norm, out_scale=out_scale, res1_scale=1.0, res2_scale=0.3, **kw)
+        Y, Y16 = Y if isinstance(Y, tuple) else (Y, None)
         names = [k for k in names if k in leaf]
         if not names:  # γ and β of a case without LayerNorm: nothing to differentiate
-            return Y.detach(), {}
+            return Y.detach(), {}, Y16
         return Y.detach(), dict(zip(names, torch.autograd.grad(Y, [leaf[k] for k in names],
-                                                                t["dY"])))
+                                                                t["dY"]))), Y16
 
-    Y, full = run(("X", "gamma", "beta", "res1", "res2"))
+    return run
+
+
+@pytest.mark.parametrize("d", [20, 64])
+@pytest.mark.parametrize("case", _PARTIAL_CASES, ids=["ln-leaky", "relu", "blend", "blend1"])
+@pytest.mark.parametrize("op", ["two_hop_fused", "att_two_hop_fused", "row_epilogue",
+                                "bipartite_hop_fused", "two_hop_fused-bf16",
+                                "att_two_hop_fused-bf16"])
+def test_partial_gradients(dev, op, case, d):
+    """The gradients of a subset of (X, γ, β, res1, res2) are bitwise those of the run in which
+    every input requires one, and Y does not depend on who asks: the backward skips what nobody
+    needs (the epilogue's kernel when neither dZ, dγ nor dβ is wanted) and nothing else. The two
+    operators over hops also with ``gather_dtype=torch.bfloat16`` (``-bf16``)."""
+    run = _partial_runner(dev, op, case, d)
+    Y, full, _ = run(_ALL_INPUTS)
     for names in _SUBSETS:
-        Ys, part = run(names)
+        Ys, part, _ = run(names)
         assert torch.equal(Ys, Y), (names, "Y")
+        for k, g in part.items():
+            assert torch.equal(g, full[k]), (names, k)
+
+
+@pytest.mark.parametrize("op", ["two_hop_fused-bf16", "att_two_hop_fused-bf16"])
+def test_partial_gradients_return_x16(dev, op):
+    """``return_x16=True`` adds the bf16 copy of Y as a second output that carries no gradient
+    and changes nothing else: Y and every gradient, of all inputs and of each subset, are bitwise
+    those of the call without it."""
+    run = _partial_runner(dev, op, _PARTIAL_CASES[0], 64)
+    Y, full, none = run(_ALL_INPUTS)
+    assert none is None
+    for names in (_ALL_INPUTS,) + tuple(_SUBSETS):
+        Yx, part, Y16 = run(names, return_x16=True)
+        assert Y16.dtype == torch.bfloat16 and Y16.requires_grad is False
+        assert torch.equal(Y16, Yx.bfloat16()) and torch.equal(Yx, Y), names
         for k, g in part.items():
             assert torch.equal(g, full[k]), (names, k)
 

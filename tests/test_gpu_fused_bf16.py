@@ -800,3 +800,52 @@ def test_encoders_gather_dtype(dev, kind, n_layers):
     for g in on[1:]:
         assert bool(g.abs().sum() > 0)
     assert not torch.equal(on[0], base[0])  # it is another path than the fp32 one
+
+
+# ---- 8. what the hops report to a HopTimer ------------------------------------------------------
+@gpu
+def test_hop_timer_records_of_the_fused_hops(dev, monkeypatch):
+    """Two records per two_hop_fused forward, one per direct spmm_csr_fused_dt call, each with
+    the byte figures of profiling.py at the element sizes of that hop: 4/4 and 4/4 in fp32; with
+    gather_dtype=bfloat16 a bf16 table into a bf16 M (2/2), then M into the float32 Y (2/4, the
+    bf16 copy of Y not counted). Never blocked, never row-ordered; a row range counts its own
+    nonzeros."""
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    from hypergraph_diffusion_for_recommendation_amd import profiling, spmm_csr_fused_dt
+    from hypergraph_diffusion_for_recommendation_amd.functional import two_hop_fused
+    monkeypatch.setenv("HGD_SPMM_BLOCKS", "0")
+    monkeypatch.setenv("HGD_SPMM_ROW_ORDER", "0")
+    n, m, d = 70, 45, 64
+    rng = np.random.default_rng(8)
+    r, c = random_coo(rng, n, m, 600)
+    key = np.unique(np.concatenate([r * m + c, 7 * m + np.arange(m)]))  # row 7: every column
+    r, c = key // m, key % m
+    inc = _inc(r, c, rng.random(len(r)) + 0.1, (n, m), dev, **_split_kw(True))
+    assert inc.csr.n_heavy > 0 and inc.val is not None
+    nnz = len(r)
+    X = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+    res = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).to(dev)
+    norm = torch.nn.LayerNorm(d).to(dev)
+    view = inc.masked(torch.from_numpy(rng.random(nnz) < 0.5), 0.5)
+    M16 = torch.from_numpy(rng.standard_normal((m, d)).astype(np.float32)).to(dev).bfloat16()
+    with profiling.HopTimer() as timer:
+        for gather_dtype in (None, BF16):
+            with torch.no_grad():
+                two_hop_fused(inc, X, P="sym", Q="mean", R="sym", norm=norm, res1=res,
+                              gather_dtype=gather_dtype)
+        Y16 = torch.empty((n, d), dtype=BF16, device=dev)
+        spmm_csr_fused_dt(view.csr, M16, nat.RowEpilogue(out_scale=1.0), val=view.val,
+                          out16=Y16, row_begin=10, row_end=50)
+    nnz_range = int(inc.csr.rowptr[50] - inc.csr.rowptr[10])
+    assert 0 < nnz_range < nnz
+    # (nonzeros, rows, has_val, has_scale, table bytes, output bytes) of every launch, in order
+    want = [(nnz, m, True, True, 4, 4), (nnz, n, True, True, 4, 4),
+            (nnz, m, True, True, 2, 2), (nnz, n, True, True, 2, 4),
+            (nnz_range, 40, True, False, 2, 4)]
+    assert len(timer.records) == len(want)
+    alg = timer.summary()["per_launch_bytes"]
+    impl = [f()[1] for _, _, f in timer.records]
+    print("hop timer:", alg, impl)
+    for k, (z, rows, hv, hs, xb, yb) in enumerate(want):
+        assert alg[k] == profiling.hop_bytes(z, rows, d, x_bytes=xb, y_bytes=yb), k
+        assert impl[k] == profiling.impl_bytes(z, rows, d, hv, hs, 0, x_bytes=xb, y_bytes=yb), k

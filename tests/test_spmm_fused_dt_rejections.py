@@ -220,6 +220,25 @@ def test_spmm_csr_fused_dt_type_errors():
         spmm_csr_fused_dt(csr, X16, ex)
 
 
+@pytest.mark.gpu
+def test_spmm_csr_fused_dt_shared_checks_keep_their_prefix(dev):
+    """The checks spmm_csr_fused_dt shares with spmm_csr answer in its own words. They come
+    after the device's refusal, so the tensors are on the device; each is still rejected before
+    anything is launched (the structure's arrays are never read)."""
+    from hypergraph_diffusion_for_recommendation_amd.incidence import spmm_csr_fused_dt
+    csr, ex = _csr(), _native.RowEpilogue(out_scale=1.0)
+    X16 = torch.zeros((2, 8), dtype=torch.bfloat16, device=dev)
+    with pytest.raises(ValueError) as e:
+        spmm_csr_fused_dt(csr, torch.zeros((5, 8), dtype=torch.bfloat16, device=dev), ex)
+    assert str(e.value) == "spmm_fused_dt: X16 has 5 rows, structure expects 2"
+    with pytest.raises(ValueError) as e:
+        spmm_csr_fused_dt(csr, X16, ex, val=torch.zeros(4, device=dev))
+    assert str(e.value) == "spmm_fused_dt: val size mismatch"
+    with pytest.raises(ValueError) as e:
+        spmm_csr_fused_dt(csr, X16, ex, row_scale=torch.zeros(2, device=dev))
+    assert str(e.value) == "spmm_fused_dt: row_scale size mismatch"
+
+
 def test_spmm_csr_still_refuses_a_16_bit_fused_hop():
     """The new path is asked for by name: spmm_csr does not infer it from a tensor's dtype."""
     from hypergraph_diffusion_for_recommendation_amd.incidence import spmm_csr
