@@ -1308,6 +1308,11 @@ hgd_status row_gemm_group(RowGemmGroup g, hipStream_t st, const char* fn) {
     const RowGemm& q = g.p[1];
     HGD_REQUIRE(q.K == p.K && q.N == p.N && (q.mask != nullptr) == (p.mask != nullptr),
                 "%s: grouped products need equal K, N and mask mode", fn);
+    // the staged kernel is instantiated per epilogue kind; every form rejects a mixed group, so
+    // that what a call accepts does not depend on the kernel the shapes and tuning keys select
+    auto epi_kind = [](const RowGemm& r) { return r.Y2 ? 1 : (r.accumulate ? 2 : 0); };
+    HGD_REQUIRE(epi_kind(q) == epi_kind(p),
+                "%s: grouped products need the same epilogue (residual / accumulate)", fn);
     if (q.rows == 0) g.count = 1;
     if (p.rows == 0) {
       g.p[0] = g.p[1];

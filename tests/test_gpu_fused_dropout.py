@@ -176,12 +176,14 @@ def _mean_pair64(H, X, G):
     return Y, dX
 
 
-@pytest.mark.parametrize("n,K,d", [(3000, 32, 64), (517, 16, 32), (2048, 128, 128)])
+@pytest.mark.parametrize("n,K,d", [(3000, 32, 64), (517, 16, 32), (2048, 128, 128),
+                                   (517, 32, 272)])
 def test_dense_mean_two_hop_matches_the_vertex_edge_means(dev, n, K, d):
     """functional.dense_mean_two_hop (V/E = nonzero(H > 0) of a dense learned hypergraph,
     HCCF_diffusion.py:382-402 + the torch_scatter mean pair) against the float64 restatement of
     the two scatter means, forward and backward; rows and columns without a positive entry
-    included (their means are 0)."""
+    included (their means are 0). d = 272 is the Python route to N > 128 on hgd_gemm_rows
+    (three column slices of the staged kernel, the last one ragged)."""
     from hypergraph_diffusion_for_recommendation_amd.functional import dense_mean_two_hop
     g = torch.Generator(device=dev).manual_seed(n + K)
     H = torch.randn(n, K, device=dev, generator=g)

@@ -192,7 +192,10 @@ def test_equivset_fused_epilogue_matches_unfused(dev):
 
 @pytest.mark.parametrize("n,K,d", [(31_668, 32, 64), (1000, 16, 32), (77, 48, 128)])
 def test_hgnn_layer_dense_two_hop(dev, n, K, d):
-    """HGNNLayer (HCCF.py:201-211) on the MFMA kernels vs float64: output and grads of H, X."""
+    """HGNNLayer (HCCF.py:201-211) on the MFMA kernels vs float64: output and grads of H, X.
+    No d > 128 case: functional._mm_ok admits 16 <= d <= 128 only, so a wider d takes the
+    library GEMM and would not reach hgd_gemm_rows (tests/test_gpu_gemm_rows_forms.py and
+    test_dense_mean_two_hop_matches_the_vertex_edge_means cover N > 128)."""
     from hypergraph_diffusion_for_recommendation_amd.layers import HGNNLayer
     torch.manual_seed(n)
     H = (torch.randn(n, K) * 0.2).to(dev).requires_grad_(True)
