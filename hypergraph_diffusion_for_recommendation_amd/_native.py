@@ -23,6 +23,7 @@ c_size = ctypes.c_size_t
 HGD_OK = 0
 EPI_NONE, EPI_LEAKY_RELU, EPI_RELU = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1  # HGD_DT_*: element types of hgd_spmm_dt / hgd_spmm_masked_dt
+PACKED_IDX_BITS, PACKED_MAX_DICT = 22, 1024  # HGD_SPMM_PACKED_IDX_BITS / _MAX_DICT
 _STATUS_NAMES = {0: "HGD_OK", 1: "HGD_ERR_INVALID_ARG", 2: "HGD_ERR_HIP",
                  3: "HGD_ERR_UNSUPPORTED", 4: "HGD_ERR_WORKSPACE"}
 
@@ -284,6 +285,13 @@ _SIGNATURES = {
     "hgd_spmm_blocked_ordered": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                                          c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32,
                                          c_f32, c_i32, c_void_p]),
+    "hgd_spmm_packed_for": (c_i32, [c_i64, c_i32, c_i64, c_i32]),
+    "hgd_spmm_packed_fits": (c_i32, [c_i64, c_i32, c_i64, c_i32]),
+    "hgd_spmm_pack_entries": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i32,
+                                      c_i32, c_i32, c_void_p, c_void_p]),
+    "hgd_spmm_blocked_packed": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p,
+                                        c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                        c_i32, c_i32, c_f32, c_i32, c_void_p]),
     "hgd_spmm_blocked_split_workspace_size": (c_size, [ctypes.POINTER(SplitPlan), c_i32, c_i32]),
     "hgd_spmm_blocked_split": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64,
                                        c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32,

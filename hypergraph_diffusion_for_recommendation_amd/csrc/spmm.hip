@@ -173,6 +173,28 @@ __global__ void block_order_dest_kernel(const int64_t* __restrict__ blk_start,
   dest[i - i % n_rows + out_row[i]] = blk_start[i];
 }
 
+// Packed entries (hgd_spmm_pack_entries): one thread per nonzero e of the block-major copy. Its
+// block is the k with bound[k] <= e < bound[k + 1] over the n_blk + 1 block boundaries
+// bound[k] = blk_start[k·n_rows] (read once per workgroup; an empty block has two equal bounds and
+// is skipped); the word is the column counted from the block's first source row beside the code
+// of the source row.
+__global__ __launch_bounds__(kBlock) void pack_entries_kernel(
+    const int64_t* __restrict__ blk_start, const int32_t* __restrict__ blk_col,
+    const int32_t* __restrict__ src_code, int64_t n_rows, int64_t n_src_rows, int64_t nnz,
+    int32_t n_blk, int32_t idx_bits, uint32_t* __restrict__ ent) {
+  __shared__ int64_t bound[65];  // (n_blk <= 64)
+  if (static_cast<int32_t>(threadIdx.x) <= n_blk)
+    bound[threadIdx.x] = blk_start[static_cast<int64_t>(threadIdx.x) * n_rows];
+  __syncthreads();
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (e >= nnz) return;
+  int32_t k = 0;
+  while (k + 1 < n_blk && e >= bound[k + 1]) ++k;
+  const int32_t c = blk_col[e];
+  const int64_t base = n_src_rows * k / n_blk;
+  ent[e] = static_cast<uint32_t>(c - base) | static_cast<uint32_t>(src_code[c]) << idx_bits;
+}
+
 // workspace of hgd_spmm_col_blocks_ordered: the block-major counts (then the permuted lengths),
 // the natural block-major starts (then the scatter's destinations), one block's keys and sorted
 // keys, then the sort's and the scan's own (one after the other in the same tail)
@@ -526,6 +548,76 @@ extern "C" hgd_status hgd_spmm_blocked_ordered(const int64_t* blk_start, const i
   r.n_blk = n_blocks;
   r.ordered = true;
   r.out_row = blk_out_row;
+  r.stream = stream;
+  return hgd::spmm_launch<float, float>(r);
+}
+
+extern "C" int32_t hgd_spmm_packed_for(int64_t n_src_rows, int32_t n_blocks, int64_t n_dict,
+                                       int32_t idx_bits) {
+  if (n_src_rows <= 0 || n_blocks < 2) return 0;  // (one block is not a blocked hop)
+  if (!hgd::packed_fits(n_src_rows, n_blocks, n_dict, idx_bits)) return 0;
+  // packing changes no sum and takes 4 of the 8 streamed bytes per nonzero away, which pays where
+  // the hop's time follows the bytes that leave L2: where the size rules run it block-ordered.
+  // The smallest slice hgd_spmm_block_order_for orders is 32 MiB of 512-byte rows (its widest
+  // pass, 128 columns); below that many source rows per block the blocks were forced, nothing
+  // was measured and the rule is off (HGD_SPMM_PACKED=1 packs wherever it fits)
+  return n_src_rows / n_blocks >= 65536 ? 1 : 0;
+}
+
+extern "C" int32_t hgd_spmm_packed_fits(int64_t n_src_rows, int32_t n_blocks, int64_t n_dict,
+                                        int32_t idx_bits) {
+  return hgd::packed_fits(n_src_rows, n_blocks, n_dict, idx_bits) ? 1 : 0;
+}
+
+extern "C" hgd_status hgd_spmm_pack_entries(const int64_t* blk_start, const int32_t* blk_col,
+                                            const int32_t* src_code, int64_t n_rows,
+                                            int64_t n_src_rows, int64_t nnz, int32_t n_blocks,
+                                            int32_t n_dict, int32_t idx_bits, uint32_t* ent,
+                                            void* stream) {
+  using namespace hgd;
+  clear_error();
+  constexpr const char* fn = "hgd_spmm_pack_entries";
+  HGD_REQUIRE(n_rows >= 0 && n_src_rows >= 0 && nnz >= 0, "%s: negative sizes", fn);
+  HGD_REQUIRE(n_blocks >= 1 && n_blocks <= 64, "%s: blocks must be 1..64", fn);
+  HGD_REQUIRE(n_src_rows < (int64_t(1) << 31), "%s: n_src_rows >= 2^31", fn);
+  HGD_REQUIRE(idx_bits >= 1 && idx_bits <= 31, "%s: idx_bits must be 1..31 (got %d)", fn, idx_bits);
+  HGD_REQUIRE(n_dict >= 1, "%s: n_dict must be >= 1 (got %d)", fn, n_dict);
+  if (!packed_fits(n_src_rows, n_blocks, n_dict, idx_bits))
+    return fail(HGD_ERR_UNSUPPORTED,
+                "%s: %d blocks of %lld source rows and %d weights do not fit %d + %d bits (at most "
+                "%d weights)", fn, n_blocks, (long long)n_src_rows, n_dict, idx_bits, 32 - idx_bits,
+                HGD_SPMM_PACKED_MAX_DICT);
+  if (nnz == 0) return HGD_OK;
+  HGD_REQUIRE(blk_start && blk_col && src_code && ent,
+              "%s: null blk_start / blk_col / src_code / ent", fn);
+  const int64_t grid = (nnz + kBlock - 1) / kBlock;
+  HGD_REQUIRE(grid <= 0x7fffffffLL, "%s: too many nonzeros", fn);
+  hipLaunchKernelGGL(pack_entries_kernel, dim3(grid), dim3(kBlock), 0, as_stream(stream),
+                     blk_start, blk_col, src_code, n_rows, n_src_rows, nnz, n_blocks, idx_bits,
+                     ent);
+  return check_launch(fn, "kernel");
+}
+
+extern "C" hgd_status hgd_spmm_blocked_packed(const int64_t* blk_start, const uint32_t* ent,
+                                              const float* dict, int32_t n_dict, int32_t idx_bits,
+                                              const float* blk_row_scale,
+                                              const int32_t* blk_out_row, int64_t n_rows,
+                                              int64_t n_src_rows, const float* X, int64_t ldx,
+                                              float* Y, int64_t ldy, int32_t d, int32_t epilogue,
+                                              float slope, int32_t n_blocks, void* stream) {
+  hgd::clear_error();
+  hgd::SpmmRequest r{"hgd_spmm_blocked_packed", nullptr, reinterpret_cast<const int32_t*>(ent),
+                     nullptr, blk_row_scale, n_rows, n_src_rows, 0, n_rows, X, ldx, Y, ldy, d,
+                     epilogue, slope};
+  r.blocked = true;
+  r.blk_start = blk_start;
+  r.n_blk = n_blocks;
+  r.ordered = true;
+  r.out_row = blk_out_row;
+  r.packed = true;
+  r.dict = dict;
+  r.n_dict = n_dict;
+  r.idx_bits = idx_bits;
   r.stream = stream;
   return hgd::spmm_launch<float, float>(r);
 }

@@ -71,6 +71,12 @@ struct SpmmArgsT {
   // from the same registers, for the next layer's hop to gather. NULL: no copy
   bf16* y16;
   int64_t ld_y16;
+  // packed entries (hgd_spmm_blocked_packed, the PK instantiations only): col holds one word per
+  // nonzero, (column − the block's first source row) | code << idx_bits, X points at the block's
+  // first source row and the weight is dict[code] (n_dict floats, copied to LDS per workgroup)
+  const float* dict;
+  int32_t n_dict;
+  int32_t idx_bits;
 };
 using SpmmArgs = SpmmArgsT<>;
 
@@ -371,19 +377,28 @@ __device__ __forceinline__ void gather_sum_mask2(const SpmmArgsT<TX, TY>& a, int
 // index batch b+1 is loaded before the gathers of batch b are issued, so the dependent
 // index → gather round trip is paid once per row instead of once per batch of G nonzeros.
 // With MASK only the kept edges are summed (same order as over the compacted matrix).
+// PK (packed entries, HAS_VAL and no MASK): the index batch is one word per nonzero, the gather
+// takes its low idx_bits as the column and the weight is looked up in wdict (the dictionary in
+// LDS) from the word's code only where the gathered row is consumed, so no weight is held in
+// registers while the gathers are in flight.
 template <int G, int VEC, int U, bool HAS_VAL, int POL, bool MASK = false, class TX = float,
-          class TY = float>
+          class TY = float, bool PK = false>
 __device__ __forceinline__ void gather_sum(const SpmmArgsT<TX, TY>& a, int64_t e0, int64_t e1,
-                                           int l, bool col_ok, float (&acc)[VEC], int32_t col0) {
+                                           int l, bool col_ok, float (&acc)[VEC], int32_t col0,
+                                           const float* wdict = nullptr) {
+  static_assert(!PK || (HAS_VAL && !MASK), "packed entries: weighted, no mask");
+  // (the index loads of a packed batch are the unweighted ones: one word)
+  constexpr bool LD_VAL = HAS_VAL && !PK;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
   const int64_t coff = static_cast<int64_t>(col0) + static_cast<int64_t>(l) * VEC;
   constexpr bool PF = (POL & kPolPrefetch) != 0;
+  [[maybe_unused]] const int cmask = PK ? static_cast<int>((1u << a.idx_bits) - 1u) : 0;
   int nxc = 0, nxk = 0;
   float nxw = 1.f;
   if constexpr (PF) {
     if (e0 < e1)
-      load_index<HAS_VAL, POL, MASK>(
+      load_index<LD_VAL, POL, MASK>(
           a, e0, static_cast<int>(min(static_cast<int64_t>(G), e1 - e0)), l, nxc, nxw, nxk);
   }
   for (int64_t eb = e0; eb < e1; eb += G) {
@@ -396,10 +411,10 @@ __device__ __forceinline__ void gather_sum(const SpmmArgsT<TX, TY>& a, int64_t e
       myk = nxk;
       const int64_t en = eb + G;
       if (en < e1)
-        load_index<HAS_VAL, POL, MASK>(
+        load_index<LD_VAL, POL, MASK>(
             a, en, static_cast<int>(min(static_cast<int64_t>(G), e1 - en)), l, nxc, nxw, nxk);
     } else {
-      load_index<HAS_VAL, POL, MASK>(a, eb, n, l, myc, myw, myk);
+      load_index<LD_VAL, POL, MASK>(a, eb, n, l, myc, myw, myk);
     }
     if constexpr (MASK) n = compact_kept<G, HAS_VAL>(a, l, myk, myc, myw);
     for (int k = 0; k < n; k += U) {
@@ -408,8 +423,9 @@ __device__ __forceinline__ void gather_sum(const SpmmArgsT<TX, TY>& a, int64_t e
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kk = k + u;
-        const int c = (G == 1) ? myc : __shfl(myc, kk, G);
-        if constexpr (HAS_VAL) w[u] = (G == 1) ? myw : __shfl(myw, kk, G);
+        int c = (G == 1) ? myc : __shfl(myc, kk, G);
+        if constexpr (PK) c &= cmask;
+        if constexpr (LD_VAL) w[u] = (G == 1) ? myw : __shfl(myw, kk, G);
         if (kk < n && col_ok) {
           load_vec<VEC, (POL & kPolNtGather) != 0>(a.X + static_cast<int64_t>(c) * a.ldx + coff,
                                                    xv[u]);
@@ -421,6 +437,10 @@ __device__ __forceinline__ void gather_sum(const SpmmArgsT<TX, TY>& a, int64_t e
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (k + u < n) {
+          if constexpr (PK) {
+            const unsigned e = static_cast<unsigned>((G == 1) ? myc : __shfl(myc, k + u, G));
+            w[u] = wdict[e >> a.idx_bits];
+          }
 #pragma unroll
           for (int i = 0; i < VEC; ++i) {
             if constexpr (HAS_VAL)
@@ -455,11 +475,17 @@ __device__ __forceinline__ void masked_or_plain_sum(const SpmmArgsT<TX, TY>& a, 
 }
 
 // ORD: the ordered hop (a.out_row set), an instantiation of its own so that every other one is
-// the code it was
+// the code it was. PK: the ordered hop over packed entries (a.dict set), one more of its own: the
+// dictionary goes to LDS once per workgroup, before any lane leaves.
 template <int G, int VEC, int U, bool HAS_VAL, int POL, bool EX, bool MASK = false,
-          class TX = float, class TY = float, bool ORD = false>
+          class TX = float, class TY = float, bool ORD = false, bool PK = false>
 __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgsT<TX, TY> a) {
   constexpr int GPB = kBlock / G;
+  __shared__ float s_dict[PK ? HGD_SPMM_PACKED_MAX_DICT : 1];  // (unused and dropped unless PK)
+  if constexpr (PK) {
+    for (int i = threadIdx.x; i < a.n_dict; i += kBlock) s_dict[i] = a.dict[i];
+    __syncthreads();
+  }
   const int g = threadIdx.x / G;
   const int l = threadIdx.x % G;
   int64_t bid = static_cast<int64_t>(blockIdx.x) - a.heavy_blocks;
@@ -499,7 +525,11 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgsT<TX, TY> a) {
   if (a.heavy_threshold > 0 && e1 - e0 > a.heavy_threshold) return;  // split-plan row
   int32_t orow = 0;  // the ordered hop's Y row: one load per row, issued ahead of the gathers
   if constexpr (ORD) orow = a.out_row[r];
-  masked_or_plain_sum<G, VEC, U, HAS_VAL, POL, MASK>(a, e0, e1, l, col_ok, acc, col0);
+  if constexpr (PK)
+    gather_sum<G, VEC, U, HAS_VAL, POL, false, TX, TY, true>(a, e0, e1, l, col_ok, acc, col0,
+                                                             s_dict);
+  else
+    masked_or_plain_sum<G, VEC, U, HAS_VAL, POL, MASK>(a, e0, e1, l, col_ok, acc, col0);
   const int64_t yr = ORD ? static_cast<int64_t>(orow) : r;
   const float s = a.row_scale ? a.row_scale[r] : 1.f;
   finish_row<G, VEC, EX, (POL & kPolNtStore) != 0, TX, TY, !MASK>(a, r, yr, s, l, coff, col_ok,

@@ -82,7 +82,24 @@ struct SpmmRequest {
   // built over block k's CSR (blk_start + k·n_rows), so a row is heavy per block; workspace is
   // then the one chunk-partial buffer the blocks reuse in stream order. plan stays NULL
   const hgd_split_plan* blk_plans = nullptr;
+  // packed entries (hgd_spmm_blocked_packed: blocked and ordered): col is the packed word per
+  // nonzero, val stays NULL and the weight of code c is dict[c]
+  bool packed = false;
+  const float* dict = nullptr;
+  int32_t n_dict = 0;
+  int32_t idx_bits = 0;
 };
+
+// Whether n_blocks source blocks over n_src_rows rows (hgd_spmm_col_blocks' cuts: the largest has
+// ⌈n_src_rows / n_blocks⌉ rows) and a dictionary of n_dict weights fit one word per nonzero with
+// idx_bits bits of block-local column: the one test of the rule, the builder and the hop.
+inline bool packed_fits(int64_t n_src_rows, int32_t n_blocks, int64_t n_dict, int32_t idx_bits) {
+  if (n_src_rows < 0 || n_blocks < 1 || n_blocks > 64 || idx_bits < 1 || idx_bits > 31) return false;
+  const int64_t widest = (n_src_rows + n_blocks - 1) / n_blocks;
+  if (widest > (int64_t(1) << idx_bits)) return false;
+  const int64_t codes = int64_t(1) << (32 - idx_bits);
+  return n_dict >= 1 && n_dict <= codes && n_dict <= HGD_SPMM_PACKED_MAX_DICT;
+}
 
 inline hgd_status check_launch(const char* fn, const char* what) {
   hipError_t e = hipGetLastError();
@@ -99,6 +116,10 @@ auto pick_kernel(const SpmmArgsT<TX, TY>& a, bool seg) {
   }
   if constexpr (G >= 8 && kSegWalk<EX, TX, TY>) {
     if (seg) return spmm_seg_kernel<G, VEC, U, HAS_VAL, POL, EX, TX, TY>;
+  }
+  if constexpr (kF32<TX, TY> && !EX && !HAS_VAL) {
+    // the ordered hop over packed entries (its request has no val: the weights are dict's)
+    if (a.dict) return spmm_kernel<G, VEC, U, true, POL, false, false, TX, TY, true, true>;
   }
   if constexpr (kF32<TX, TY> && !EX) {
     // the ordered hop (no mask, no segmented walk: spmm_check_args)
@@ -215,6 +236,17 @@ inline hgd_status spmm_check_args(const SpmmRequest& r) {
               r.blocked ? "blk_out_row" : "out_row");
   HGD_REQUIRE(!r.blocked || (r.n_blk >= 1 && r.n_blk <= 64), "%s: blocks must be 1..64", fn);
   HGD_REQUIRE(!r.blocked || r.blk_start || r.row_end <= r.row_begin, "%s: null blk_start", fn);
+  if (r.packed) {  // (an entry point of its own: blocked and ordered)
+    HGD_REQUIRE(r.idx_bits >= 1 && r.idx_bits <= 31, "%s: idx_bits must be 1..31 (got %d)", fn,
+                r.idx_bits);
+    HGD_REQUIRE(r.n_dict >= 1, "%s: n_dict must be >= 1 (got %d)", fn, r.n_dict);
+    HGD_REQUIRE(r.dict || empty, "%s: null dict", fn);
+    if (r.n_src_rows >= 0 && !packed_fits(r.n_src_rows, r.n_blk, r.n_dict, r.idx_bits))
+      return fail(HGD_ERR_UNSUPPORTED,
+                  "%s: %d blocks of %lld source rows and %d weights do not fit %d + %d bits (at "
+                  "most %d weights)", fn, r.n_blk, (long long)r.n_src_rows, r.n_dict, r.idx_bits,
+                  32 - r.idx_bits, HGD_SPMM_PACKED_MAX_DICT);
+  }
   if (r.blocked && r.blk_plans) {
     // a block with split rows is walked by the row kernel, one without by hgd_spmm_blocked's
     // choice (HGD_TUNE_SPMM_BLOCKED_SEG): a plan has no say in it
@@ -300,6 +332,11 @@ hgd_status spmm_fill_args(SpmmArgsT<TX, TY>& a, const SpmmRequest& r) {
   a.inv_keep = pow2 ? 1.f / r.keep : 0.f;
   a.mask_pair = t.mask_pair;
   a.out_row = r.out_row;
+  if (r.packed) {
+    a.dict = r.dict;
+    a.n_dict = r.n_dict;
+    a.idx_bits = r.idx_bits;
+  }
   a.y16 = static_cast<bf16*>(r.y16);
   a.ld_y16 = r.ld_y16;
   const hgd_split_plan* plan = r.plan;
@@ -450,6 +487,8 @@ hgd_status spmm_passes(SpmmArgsT<TX, TY> a, const SpmmRequest& r, const SpmmPass
         if (r.ordered) {  // ... in its own row order (the row kernel only: no segmented walk)
           a.out_row = r.out_row + static_cast<int64_t>(k) * r.n_rows;
           if (r.row_scale) a.row_scale = r.row_scale + static_cast<int64_t>(k) * r.n_rows;
+          if (r.packed)  // a packed column counts from the block's first source row
+            a.X = static_cast<const TX*>(r.X) + r.n_src_rows * k / r.n_blk * r.ldx;
         } else if constexpr (kF32<TX, TY>) {
           if (VEC == 4) a.seg = spmm_tuning().blocked_seg;  // (the vector path's only)
         }

@@ -130,7 +130,8 @@ class _TwoHop(torch.autograd.Function):
         q = inc.scale("col", Q)
         # hop 1 into the columns (hyperedges) of A: M = Q·Aᵀ·(R·X), stored in X's dtype (a bf16
         # table gives a bf16 M: the second hop's gather is halved too)
-        M = spmm_csr(inc.csc, X, val=inc.edge_values("csc", R), row_scale=q)
+        M = spmm_csr(inc.csc, X, val=inc.edge_values("csc", R), row_scale=q,
+                     src_scale=inc.edge_src_scale("csc", R))
         # hop 2 back into the rows (vertices): Z = P·A·M, and the activation
         ctx.inc = inc
         ctx.scales = (P, Q, R)
@@ -144,7 +145,7 @@ class _TwoHop(torch.autograd.Function):
         q = inc.scale("col", Q)
         # dM in the dtype M had (X's), dX in X's
         dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q,
-                      out_dtype=ctx.x_dtype)
+                      out_dtype=ctx.x_dtype, src_scale=inc.edge_src_scale("csc", P))
         r = inc.scale("row", R)
         dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=r, out_dtype=ctx.x_dtype)
         return dX, None, None, None, None, None, None, None
@@ -345,7 +346,8 @@ class _FusedTwoHop(torch.autograd.Function):
                 x16, return_x16: bool):
         P, Q, R = scales
         M = spmm_csr(inc.csc, _table16(X, x16) if gather16 else X.contiguous(),
-                     val=inc.edge_values("csc", R), row_scale=inc.scale("col", Q))
+                     val=inc.edge_values("csc", R), row_scale=inc.scale("col", Q),
+                     src_scale=inc.edge_src_scale("csc", R))
         ex = _row_epilogue_setup(ctx, inc.n_rows, X.shape[1], X.device, gamma, beta, res1, res2,
                                  cfg)
         ctx.inc, ctx.scales, ctx.gather16 = inc, scales, gather16
@@ -370,7 +372,8 @@ class _FusedTwoHop(torch.autograd.Function):
                      if q is None else q * dz_scale)
             g16 = ctx.gather16
             dM = spmm_csr(inc.csc, dZ, val=inc.edge_values("csc", P), row_scale=q,
-                          out_dtype=torch.bfloat16 if g16 else None)
+                          out_dtype=torch.bfloat16 if g16 else None,
+                          src_scale=inc.edge_src_scale("csc", P))
             dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=inc.scale("row", R),
                           out_dtype=torch.float32 if g16 else None)
         return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None, None

@@ -92,6 +92,7 @@ class CSR:
         self._blk_ws_bytes: Dict[Tuple[int, int], int] = {}
         self._col_blocks_ord: Dict[int, Tuple[torch.Tensor, ...]] = {}
         self._blk_ord_vals: Dict[Tuple[int, int], tuple] = {}
+        self._packed: Dict[Tuple[int, int, int], tuple] = {}
         self._row_order: Optional[Tuple[torch.Tensor, ...]] = None
         self._ord_vals: Dict[Tuple[int, int], tuple] = {}
         self._plan_arrays = ()
@@ -286,6 +287,47 @@ class CSR:
         return _gather32_cached(self._blk_ord_vals, 2 * n_blocks + 1, row_scale,
                                 self.col_blocks_ordered(n_blocks)[3])
 
+    def packed_entries(self, n_blocks: int, src_scale: torch.Tensor,
+                       idx_bits: int = nat.PACKED_IDX_BITS) -> Optional[tuple]:
+        """The entries of :meth:`col_blocks_ordered` packed for hgd_spmm_blocked_packed, for
+        per-nonzero weights that are ``src_scale[col]`` (a float32 scale over this structure's
+        ``n_cols`` source rows): ``(ent [nnz] int32 bits, dict [n_dict] float32, n_dict)`` with
+        ``ent = (col − first source row of the block) | code << idx_bits`` and ``dict[code]`` the
+        weight — the distinct values of ``src_scale`` by bit pattern, so ``dict[code of c]`` is
+        ``src_scale[c]`` bit for bit. ``None`` when a block has more than ``2^idx_bits`` source
+        rows or the scale too many distinct values (hgd_spmm_packed_fits). The dictionary size is
+        read from the device once per scale tensor; the result is cached per (block count, bits,
+        tensor) while the tensor is alive and unmodified, like :meth:`blocked_values`, so the
+        weight copy of :meth:`blocked_ordered_values` is never built on this path."""
+        try:
+            version = src_scale._version
+        except RuntimeError:  # an inference tensor tracks no version: built every call
+            version = None
+        key = (n_blocks, idx_bits, id(src_scale))
+        hit = self._packed.get(key)
+        if (hit is not None and version is not None and hit[0]() is src_scale
+                and hit[1] == version):
+            return hit[2]
+        if src_scale.dtype != torch.float32 or src_scale.numel() != self.n_cols:
+            raise ValueError("packed_entries: src_scale must be float32 [n_cols]")
+        lib = nat.load()
+        bits, code = torch.unique(src_scale.contiguous().view(torch.int32), return_inverse=True)
+        n_dict = int(bits.numel())
+        got = None
+        if lib.hgd_spmm_packed_fits(self.n_cols, n_blocks, n_dict, idx_bits):
+            start, bcol, _, _ = self.col_blocks_ordered(n_blocks)
+            code = code.to(torch.int32)
+            ent = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
+            nat.check(lib.hgd_spmm_pack_entries(
+                start.data_ptr(), bcol.data_ptr(), code.data_ptr(), self.n_rows, self.n_cols,
+                self.nnz, n_blocks, n_dict, idx_bits, ent.data_ptr(), _stream(self.device)),
+                "hgd_spmm_pack_entries")
+            got = (ent, bits.view(torch.float32), n_dict)
+        if len(self._packed) >= 8:
+            self._packed.pop(next(iter(self._packed)))
+        self._packed[key] = (weakref.ref(src_scale), version, got)
+        return got
+
     def row_order(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """The rows in ascending order of their smallest column, for the ordered hop
         (hgd_spmm_row_order): ``(order [n_rows] int32, rowptr_o [n_rows+1] int64, col_o [nnz]
@@ -461,6 +503,36 @@ def spmm_block_order(csr: CSR, d: int, blocks: int) -> bool:
                                                     int(blocks)))
 
 
+def spmm_packed(csr: CSR, blocks: int, src_scale: Optional[torch.Tensor]) -> Optional[tuple]:
+    """The packed entries the fp32 block-ordered hop over ``csr`` in ``blocks`` blocks runs on
+    (hgd_spmm_blocked_packed over :meth:`CSR.packed_entries`), or ``None`` for the weighted hop.
+
+    When the weights are a scale over the source rows expanded per nonzero (``src_scale``: the
+    degree scales of a binary incidence, a few dozen distinct values), a nonzero is one word —
+    its column inside the block and a 10-bit code of its weight — instead of a column and a
+    weight: half the streamed index bytes, the same fmaf chains, Y bitwise
+    hgd_spmm_blocked_ordered's. It fits (hgd_spmm_packed_fits) when every block is within 2^22
+    source rows and the scale has at most 1024 distinct values; the rule is the library's
+    (hgd_spmm_packed_for): it fits and the blocks are as large as the size rules
+    make them, at least 65,536 source rows each.
+
+    ``HGD_SPMM_PACKED``: ``0`` off, ``1`` on wherever it fits, unset (or ``auto``) = the rule."""
+    if blocks <= 1 or csr.nnz == 0:
+        return None
+    env = os.environ.get("HGD_SPMM_PACKED", "")
+    if env not in ("", "auto", "0", "1"):
+        raise ValueError(f"HGD_SPMM_PACKED must be 0 or 1, got {env!r}")
+    rule = nat.load().hgd_spmm_packed_for
+    if env == "0" or src_scale is None:
+        return None
+    if env != "1" and not rule(csr.n_cols, int(blocks), 1, nat.PACKED_IDX_BITS):
+        return None  # (not even with one weight: the scale's are not counted for nothing)
+    got = csr.packed_entries(int(blocks), src_scale)
+    if got is None or env == "1":
+        return got
+    return got if rule(csr.n_cols, int(blocks), got[2], nat.PACKED_IDX_BITS) else None
+
+
 # element types of the hop's table and output -> HGD_DT_* (hgd_spmm_dt)
 _HOP_DTYPES = {torch.float32: nat.DT_F32, torch.bfloat16: nat.DT_BF16}
 
@@ -477,8 +549,15 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
              row_begin: int = 0, row_end: Optional[int] = None,
              ex: Optional[nat.RowEpilogue] = None, blocks: Optional[int] = None,
              out_dtype: Optional[torch.dtype] = None, _fused16: bool = False,
-             _out16: Optional[torch.Tensor] = None) -> torch.Tensor:
+             _out16: Optional[torch.Tensor] = None,
+             src_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``Y[r] = epi(row_scale[r] * Σ_e val[e] * X[col[e]])`` for r in [row_begin, row_end).
+
+    ``src_scale`` (float32 ``[n_cols]``): the caller's statement that ``val`` is that scale over
+    the source rows expanded per nonzero, ``val[e] = src_scale[col[e]]`` bit for bit. The fp32
+    block-ordered hop then runs on packed entries without the weight stream when
+    :func:`spmm_packed` says so (hgd_spmm_blocked_packed, the same Y bit for bit); every other
+    hop reads ``val`` as without it, so ``src_scale`` without ``val`` on such a hop is an error.
 
     ``X`` is float32 or bfloat16; the result is ``out.dtype`` if ``out`` is given, else
     ``out_dtype``, else ``X.dtype``. Float32 in and out is hgd_spmm (and its masked / blocked /
@@ -562,7 +641,22 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     # and the fp32 source-blocked hop over the whole row range each block's rows in its own
     blk_ordered = (not dt and bool(blocks) and rb == 0 and re_ == n
                    and spmm_block_order(csr, d, blocks))
-    if ordered:
+    # ... on packed entries when the weights are a source-row scale with few distinct values
+    packed = spmm_packed(csr, blocks, src_scale) if blk_ordered else None
+    if src_scale is not None:
+        if src_scale.dtype != torch.float32 or src_scale.numel() != m:
+            raise ValueError(f"{_hop_names(_fused16)[0]}: src_scale must be float32 [n_cols]")
+        if val is None and packed is None:
+            raise ValueError(f"{_hop_names(_fused16)[0]}: src_scale without val on a hop that "
+                             "does not run on packed entries (pass the expanded val beside it)")
+    if packed is not None:
+        start, _, _, out_row = csr.col_blocks_ordered(blocks)
+        ent, wdict, n_dict = packed
+        nat.check(lib.hgd_spmm_blocked_packed(
+            start.data_ptr(), ent.data_ptr(), wdict.data_ptr(), n_dict, nat.PACKED_IDX_BITS,
+            nat.ptr(csr.blocked_ordered_scale(blocks, row_scale)), out_row.data_ptr(), n, m, xp,
+            ldx, yp, ldy, d, int(epilogue), float(slope), blocks, st), "hgd_spmm_blocked_packed")
+    elif ordered:
         order, rowptr_o, col_o, _ = csr.row_order()
         nat.check(lib.hgd_spmm_ordered(
             rowptr_o.data_ptr(), col_o.data_ptr(), nat.ptr(csr.ordered_values(val)),
@@ -645,14 +739,16 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
         def nbytes(csr=csr, rb=rb, re_=re_, full=full, d=d, hv=val is not None,
                    hs=row_scale is not None, blocks=blocks or split_blocks,
                    xb=X.element_size(), yb=out.element_size(), ordered=ordered,
-                   blk_ordered=blk_ordered, split=bool(split_blocks)):
+                   blk_ordered=blk_ordered, split=bool(split_blocks),
+                   packed=packed is not None):
             nnz = csr.nnz if full else int(csr.rowptr[re_].item() - csr.rowptr[rb].item())
             # (the chunks of every split row: a row range runs those of its own rows only)
             chunks = sum(int(p.n_chunks) for p in csr.col_block_plans(blocks)) if split else 0
             return (profiling.hop_bytes(nnz, re_ - rb, d, x_bytes=xb, y_bytes=yb),
                     profiling.impl_bytes(nnz, re_ - rb, d, hv, hs, blocks, x_bytes=xb,
                                          y_bytes=yb, ordered=ordered,
-                                         block_ordered=blk_ordered, split_chunks=chunks))
+                                         block_ordered=blk_ordered, split_chunks=chunks,
+                                         packed=packed))
 
         timer.end(t0, nbytes)
     return out
@@ -1026,6 +1122,15 @@ class Incidence:
                 out.data_ptr(), _stream(self.device)), "hgd_edge_values")
         self._edge_vals[key] = out
         return out
+
+    def edge_src_scale(self, orient: str, src_kind: Optional[str]) -> Optional[torch.Tensor]:
+        """The scale over the gathered side that :meth:`edge_values` of the same arguments is
+        the plain expansion of (``w[e] = S[src(e)]``), for ``spmm_csr(..., src_scale=)``; ``None``
+        when the matrix has values of its own folded in, or no source scale."""
+        base = self.val if orient == "csr" else self.val_t
+        if base is not None:
+            return None
+        return self.scale("col" if orient == "csr" else "row", src_kind)
 
     def to_dense_cpu(self) -> torch.Tensor:
         """Debug helper: the matrix as a dense CPU tensor (test use)."""

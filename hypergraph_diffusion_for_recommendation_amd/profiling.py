@@ -37,7 +37,7 @@ def hop_bytes(nnz: int, rows: int, d: int, weighted: bool = False, x_bytes: int 
 
 def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
                blocks: int = 0, x_bytes: int = 4, y_bytes: int = 4, ordered: bool = False,
-               block_ordered: bool = False, split_chunks: int = 0) -> int:
+               block_ordered: bool = False, split_chunks: int = 0, packed: bool = False) -> int:
     """Bytes the hgd_spmm launch streams at minimum as implemented (int64 rowptr, weights).
     A source-blocked hop (hgd_spmm_blocked, ``blocks`` = P > 1) reads the [R × (P+1)] int64
     block starts instead of the rowptr, writes every Y row P times, reads it back P−1 times and
@@ -48,7 +48,12 @@ def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
     (hgd_spmm_blocked_ordered, ``block_ordered``) the one of every row in every block. A blocked
     hop over split rows (hgd_spmm_blocked_split, ``split_chunks`` = the chunks of all its blocks'
     plans) also writes the fp32 partial of every chunk once and reads it once in the fix-up,
-    with the chunk's int32 owner."""
+    with the chunk's int32 owner. A block-ordered hop on packed entries (hgd_spmm_blocked_packed,
+    ``packed``) reads one word per nonzero, column and weight code together: the 4 bytes per
+    nonzero of the weight stream are gone (``has_val`` says the hop is weighted all the same)."""
+    if packed and blocks > 1 and block_ordered:
+        return (impl_bytes(nnz, rows, d, has_val, has_scale, blocks, x_bytes, y_bytes,
+                           block_ordered=True) - (4 * nnz if has_val else 0))
     if split_chunks:
         return (impl_bytes(nnz, rows, d, has_val, has_scale, blocks, x_bytes, y_bytes)
                 + split_chunks * (2 * 4 * d + 4))

@@ -599,6 +599,11 @@ class ShardedIncidence:
         d = X.shape[1]
         Y = torch.empty((inc.n_rows, d), dtype=torch.float32, device=X.device)
         val_t = inc.edge_values("csc", src_kind)
+        # one chunk covers all rows: that hop may run on packed entries, told what val_t was
+        # expanded from (a row range never does, so the chunked hops are the calls they were)
+        whole = {}
+        if self.bounds == [(0, inc.n_cols)]:
+            whole = {"src_scale": inc.edge_src_scale("csc", src_kind)}
         row_scale = inc.scale("row", dst_kind)
         use_p2p = self.transport == "p2p" and self.world > 1
         sl = self.slices(d)
@@ -634,7 +639,7 @@ class ShardedIncidence:
                 Ms = torch.empty((inc.n_cols, w), dtype=torch.float32, device=X.device)
                 for a, b in self.bounds:
                     spmm_csr(inc.csc, Xs, val=val_t, row_scale=self.q, out=Ms, row_begin=a,
-                             row_end=b)
+                             row_end=b, **whole)
                     if self.world > 1:
                         works.append(ordered_all_reduce(Ms[a:b], group=self.group,
                                                         async_op=True))

@@ -21,6 +21,8 @@
  *   hgd_spmm_blocked_dt      the source-blocked hop over bfloat16 tables
  *   hgd_spmm_blocked_ordered the source-blocked hop with each block's rows walked in ascending
  *                            order of their first column (hgd_spmm_col_blocks_ordered builds it)
+ *   hgd_spmm_blocked_packed  hgd_spmm_blocked_ordered over one packed word per nonzero (block-local
+ *                            column + weight code), for weights expanded from a per-row scale
  *   hgd_spmm_blocked_split   the source-blocked hop over a structure with split rows (a split
  *                            plan per source block)
  *   hgd_sort_perm            COO→CSR / CSR→CSC ordering that cuSPARSE re-derives per call
@@ -387,6 +389,54 @@ hgd_status hgd_spmm_blocked_ordered(const int64_t* blk_start, const int32_t* blk
                                     int64_t n_src_rows, const float* X, int64_t ldx, float* Y,
                                     int64_t ldy, int32_t d, int32_t epilogue, float slope,
                                     int32_t n_blocks, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * hgd_spmm_blocked_ordered WITHOUT THE WEIGHT STREAM, for weights that are a per-source-row scale
+ * expanded over the nonzeros (val[e] = S[col[e]], the degree scales of a binary incidence:
+ * torch.sparse.mm(adj.t(), X) with adj = D^-1/2 H ..., model/graph/HGNN_HD4.py:459-462): S has few
+ * distinct values, so a nonzero is ONE 32-bit word
+ *   ent = (col − base_k) | code << idx_bits
+ * with base_k = ⌊n_src_rows·k / n_blocks⌋ the first source row of its block k (hgd_spmm_col_blocks'
+ * cuts) and dict[code] the weight. The hop reads 4 bytes per nonzero instead of 8; each piece is
+ * the same fmaf chain over the same weights, so Y is bitwise hgd_spmm_blocked_ordered's with
+ * blk_val[e] = dict[code of e].
+ *
+ * idx_bits is 1..31 (22 by default: a block of at most 4 Mi source rows beside a 10-bit code);
+ * every block must have at most 2^idx_bits source rows and the dictionary 1..min(2^(32−idx_bits),
+ * HGD_SPMM_PACKED_MAX_DICT) entries (it lives in 4 KB of LDS), else HGD_ERR_UNSUPPORTED.
+ *
+ * hgd_spmm_pack_entries builds ent [nnz] (uint32) from blk_start / blk_col of
+ * hgd_spmm_col_blocks_ordered (or hgd_spmm_col_blocks) and src_code [n_src_rows] (int32, every
+ * code < n_dict: trusted as the columns are), one thread per nonzero, which finds its block from
+ * the n_blocks + 1 block boundaries blk_start[k·n_rows]. No atomics, no workspace, stream-ordered,
+ * no host synchronisation. nnz is the caller's (blk_start[n_blocks·n_rows]).
+ *
+ * hgd_spmm_blocked_packed: hgd_spmm_blocked_ordered's arguments with ent in place of blk_col /
+ * blk_val, plus the dictionary. Refuses what hgd_spmm_blocked_ordered refuses.
+ * ---------------------------------------------------------------------------------------- */
+#define HGD_SPMM_PACKED_MAX_DICT 1024
+#define HGD_SPMM_PACKED_IDX_BITS 22
+/* hgd_spmm_packed_fits: 1 when the format can hold the hop (n_blocks in 1..64, every block within
+ * 2^idx_bits source rows, 1 <= n_dict <= min(2^(32−idx_bits), HGD_SPMM_PACKED_MAX_DICT)): what the
+ * builder and the hop accept.
+ * hgd_spmm_packed_for: the rule both hosts use: 1 when a block-ordered hop
+ * gathering n_src_rows rows in n_blocks >= 2 source blocks whose weights have n_dict distinct values
+ * should run packed at idx_bits — it fits, and a block has at least 65,536 source rows (the
+ * smallest slice hgd_spmm_block_order_for orders: below it the blocks were forced). */
+int32_t hgd_spmm_packed_fits(int64_t n_src_rows, int32_t n_blocks, int64_t n_dict,
+                             int32_t idx_bits);
+int32_t hgd_spmm_packed_for(int64_t n_src_rows, int32_t n_blocks, int64_t n_dict,
+                            int32_t idx_bits);
+hgd_status hgd_spmm_pack_entries(const int64_t* blk_start, const int32_t* blk_col,
+                                 const int32_t* src_code, int64_t n_rows, int64_t n_src_rows,
+                                 int64_t nnz, int32_t n_blocks, int32_t n_dict, int32_t idx_bits,
+                                 uint32_t* ent, void* stream);
+hgd_status hgd_spmm_blocked_packed(const int64_t* blk_start, const uint32_t* ent,
+                                   const float* dict, int32_t n_dict, int32_t idx_bits,
+                                   const float* blk_row_scale, const int32_t* blk_out_row,
+                                   int64_t n_rows, int64_t n_src_rows, const float* X, int64_t ldx,
+                                   float* Y, int64_t ldy, int32_t d, int32_t epilogue, float slope,
+                                   int32_t n_blocks, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * hgd_spmm_blocked (fp32 in and out, a row range honoured) over a structure WITH SPLIT ROWS: the
