@@ -1180,6 +1180,8 @@ def drop_edges(indices: torch.Tensor, values: torch.Tensor, mask: torch.Tensor,
         count = int(m.sum().item()) if nnz else 0
     out_idx = torch.empty((2, count), dtype=torch.int64, device=device)
     out_val = torch.empty(count, dtype=torch.float32, device=device)
+    if count == 0:  # nothing kept: nothing to write (the library takes no null output arrays)
+        return out_idx, out_val
     ws = _ws(lib.hgd_dropedge_workspace_size(nnz), device)
     nat.check(lib.hgd_dropedge_compact(
         rows.data_ptr() if nnz else None, cols.data_ptr() if nnz else None,
