@@ -131,8 +131,9 @@ extern "C" hgd_status hgd_rank_metrics(const int32_t* ids, int64_t n_rows, int64
   }
   if (n_rows == 0) return HGD_OK;
   HGD_REQUIRE(ids && test_rowptr && discount && hits && dcg, "hgd_rank_metrics: null pointer");
+  // the same row limit as hgd_topk_rows, whose lists these are
+  if (n_rows > 0x7fffffffLL) return fail(HGD_ERR_UNSUPPORTED, "hgd_rank_metrics: too many rows");
   const int64_t blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-  HGD_REQUIRE(blocks <= 0x7fffffffLL, "hgd_rank_metrics: too many rows");
   hipLaunchKernelGGL(k_rank_metrics, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
                      as_stream(stream), ids, n_rows, ld, static_cast<int>(k), test_rowptr,
                      test_cols, cut, discount, hits, dcg);

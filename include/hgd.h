@@ -990,7 +990,8 @@ hgd_status hgd_topk_rows(const float* scores, int64_t n_rows, int64_t n_cols, in
  * of row r are test_cols[test_rowptr[r] : test_rowptr[r+1]] (device, ascending, distinct
  * internal item ids); discount float64 [k] (device) = 1.0/math.log(n+2, 2) computed by the host
  * so DCG is bit-identical to the reference; cutoffs = the N values (HOST array, ascending, in
- * [1, k], at most 16). Outputs hits int32 / dcg float64 [n_rows, n_cutoffs]. */
+ * [1, k], at most 16). Outputs hits int32 / dcg float64 [n_rows, n_cutoffs].
+ * All three entries: n_rows = 0 launches nothing; n_rows > 2^31 - 1 is HGD_ERR_UNSUPPORTED. */
 hgd_status hgd_rank_metrics(const int32_t* ids, int64_t n_rows, int64_t ld, int32_t k,
                             const int64_t* test_rowptr, const int32_t* test_cols,
                             const int32_t* cutoffs, int32_t n_cutoffs, const double* discount,

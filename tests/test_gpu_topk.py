@@ -30,7 +30,9 @@ def test_topk_rows_matches_find_k_largest(dev, k, n_cols):
     for r in range(rows):
         ref_ids, ref_sc = O.topk_closed_form(k, S[r])
         assert ids[r].tolist() == ref_ids, (r, ids[r][:10], ref_ids[:10])
-        np.testing.assert_array_equal(sc[r], np.asarray(ref_sc, dtype=np.float32))
+        # as bit patterns: row 5's -0.0 must come back as -0.0
+        np.testing.assert_array_equal(sc[r].view(np.uint32),
+                                      np.asarray(ref_sc, dtype=np.float32).view(np.uint32))
     if n_cols == 300 and k <= 40:  # the literal numba restatement on a few rows
         for r in range(0, rows, 5):
             assert ids[r].tolist() == O.find_k_largest(k, S[r])[0]
