@@ -327,6 +327,10 @@ _SIGNATURES = {
                                           c_i64, c_i32, c_i32, c_f32, c_i32, c_f32, c_void_p,
                                           c_i64, c_void_p, c_void_p, c_void_p, c_size,
                                           c_void_p]),
+    "hgd_row_epilogue_backward_dt": (c_i32, [c_void_p, c_i64, c_void_p, c_i64, c_void_p,
+                                             c_void_p, c_i64, c_i32, c_i32, c_f32, c_i32, c_f32,
+                                             c_void_p, c_i32, c_i64, c_void_p, c_void_p,
+                                             c_void_p, c_size, c_void_p]),
     "hgd_linear_forward": (c_i32, [c_void_p, c_i64, c_i64, c_i32, c_void_p, c_i64, c_i32,
                                    c_void_p, c_i32, c_void_p, c_i64, c_void_p]),
     "hgd_linear_backward_data": (c_i32, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i32,

@@ -69,6 +69,7 @@ struct bf16 {
 };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float bf16_widen(uint32_t bits) { return __uint_as_float(bits << 16); }
 
@@ -93,7 +94,8 @@ __device__ __forceinline__ void load_vec(const bf16* p, float (&v)[VEC]) {
   }
 }
 
-// VEC floats rounded to bf16 (round-to-nearest-even) and stored (one 16-byte access when VEC == 8).
+// VEC floats rounded to bf16 (round-to-nearest-even) and stored (one 16-byte access when VEC == 8,
+// one 8-byte access when VEC == 4).
 template <int VEC, bool NT = false>
 __device__ __forceinline__ void store_vec(bf16* p, const float (&v)[VEC]) {
   if constexpr (VEC == 8) {
@@ -102,6 +104,10 @@ __device__ __forceinline__ void store_vec(bf16* p, const float (&v)[VEC]) {
                      bf16_round(v[4]) | (bf16_round(v[5]) << 16),
                      bf16_round(v[6]) | (bf16_round(v[7]) << 16)};
     *reinterpret_cast<u32x4*>(p) = t;
+  } else if constexpr (VEC == 4) {
+    const u32x2 t = {bf16_round(v[0]) | (bf16_round(v[1]) << 16),
+                     bf16_round(v[2]) | (bf16_round(v[3]) << 16)};
+    *reinterpret_cast<u32x2*>(p) = t;
   } else {
 #pragma unroll
     for (int i = 0; i < VEC; ++i) p[i].bits = static_cast<uint16_t>(bf16_round(v[i]));

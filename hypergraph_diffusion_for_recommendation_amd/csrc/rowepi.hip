@@ -9,6 +9,11 @@
 // combines its lane groups in LDS in group order and writes one partial row; a second kernel sums
 // the partials in block order. The grid size depends only on (n_rows, d), so the result is
 // deterministic run to run.
+//
+// hgd_row_epilogue_backward_dt stores dZ in bfloat16 for backward hops that gather 16-bit tables:
+// the same kernel with the store type TZ = bf16. The arithmetic is the fp32 one throughout and
+// dγ / dβ are folded from the unrounded values; only the store differs, one round to nearest even
+// from the registers that hold the finished row (four bf16 per lane as one 8-byte store).
 #include "device_util.h"
 #include "hgd_internal.h"
 
@@ -31,14 +36,17 @@ struct RowEpiBwd {
   float slope;
   int32_t ln;
   float out_scale;
-  float* dZ;
+  void* dZ;  // [n, ldz] of the kernel's TZ
   int64_t ldz;
   float* part_g;  // [gridDim.x, d] or NULL
   float* part_b;
 };
 
-template <int G, int VEC>
-__global__ __launch_bounds__(kBlock) void k_rowepi_bwd(RowEpiBwd p) {
+// The bf16 store's rounding took the 32- and 64-lane float4 forms to 65 / 67 VGPRs, one wave per
+// SIMD below the fp32 forms (62 / 64); asked for 8 waves they fit 64 without scratch. The fp32
+// instantiations are built as before.
+template <int G, int VEC, typename TZ>
+__global__ __launch_bounds__(kBlock, sizeof(TZ) == 2 ? 8 : 1) void k_rowepi_bwd(RowEpiBwd p) {
   constexpr int GPB = kBlock / G;
   __shared__ float s_g[GPB * G * VEC];
   __shared__ float s_b[GPB * G * VEC];
@@ -98,7 +106,7 @@ __global__ __launch_bounds__(kBlock) void k_rowepi_bwd(RowEpiBwd p) {
 #pragma unroll
       for (int i = 0; i < VEC; ++i) da[i] = a[i] > 0.f ? da[i] : 0.f;
     }
-    if (col_ok) store_vec<VEC>(p.dZ + r * p.ldz + coff, da);
+    if (col_ok) store_vec<VEC>(static_cast<TZ*>(p.dZ) + r * p.ldz + coff, da);
   }
   if (!p.part_g) return;  // block-uniform
 #pragma unroll
@@ -204,17 +212,17 @@ __global__ __launch_bounds__(kBlock) void k_rowepi_fwd(RowEpiFwd p) {
   }
 }
 
-template <int VEC>
-hgd_status launch(int G, const RowEpiBwd& p, int64_t blocks, hipStream_t st) {
+template <int VEC, typename TZ>
+hgd_status launch(const char* fn, int G, const RowEpiBwd& p, int64_t blocks, hipStream_t st) {
   switch (G) {
-#define HGD_CASE(GG)                                                                      \
-    case GG:                                                                              \
-      hipLaunchKernelGGL((k_rowepi_bwd<GG, VEC>), dim3(blocks), dim3(kBlock), 0, st, p);  \
-      return check_launch("hgd_row_epilogue_backward");
+#define HGD_CASE(GG)                                                                          \
+    case GG:                                                                                  \
+      hipLaunchKernelGGL((k_rowepi_bwd<GG, VEC, TZ>), dim3(blocks), dim3(kBlock), 0, st, p);  \
+      return check_launch(fn);
     HGD_CASE(1) HGD_CASE(2) HGD_CASE(4) HGD_CASE(8) HGD_CASE(16) HGD_CASE(32) HGD_CASE(64)
 #undef HGD_CASE
     default:
-      return fail(HGD_ERR_UNSUPPORTED, "hgd_row_epilogue_backward: group size %d", G);
+      return fail(HGD_ERR_UNSUPPORTED, "%s: group size %d", fn, G);
   }
 }
 
@@ -247,21 +255,23 @@ extern "C" size_t hgd_row_epilogue_backward_workspace_size(int64_t n_rows, int32
   return 2 * hgd::align_up(static_cast<size_t>(hgd::kMaxBlocks) * static_cast<size_t>(d) * 4);
 }
 
-extern "C" hgd_status hgd_row_epilogue_backward(const float* dY, int64_t ldy, const float* act_out,
-                                                int64_t ld_act, const float* stats,
-                                                const float* ln_gamma, int64_t n_rows, int32_t d,
-                                                int32_t act, float slope, int32_t layer_norm,
-                                                float out_scale, float* dZ, int64_t ldz,
-                                                float* dgamma, float* dbeta, void* workspace,
-                                                size_t workspace_bytes, void* stream) {
-  using namespace hgd;
-  clear_error();
-  HGD_REQUIRE(d > 0 && n_rows >= 0, "hgd_row_epilogue_backward: bad sizes");
-  HGD_REQUIRE(act >= HGD_EPI_NONE && act <= HGD_EPI_RELU, "hgd_row_epilogue_backward: bad act");
-  HGD_REQUIRE(act == HGD_EPI_NONE || slope >= 0.f,
-              "hgd_row_epilogue_backward: activation needs slope >= 0");
-  HGD_REQUIRE(layer_norm == 0 || layer_norm == 1, "hgd_row_epilogue_backward: layer_norm 0/1");
-  HGD_REQUIRE(ldy >= d && ldz >= d, "hgd_row_epilogue_backward: ldy/ldz < d");
+namespace hgd {
+namespace {
+
+// hgd_row_epilogue_backward (z16 = false: dZ is float) and the bf16 arm of
+// hgd_row_epilogue_backward_dt (z16 = true: dZ is bf16, ldz in bf16 elements), each in its own
+// name fn. Every check returns before the first launch.
+hgd_status row_epilogue_backward(const char* fn, const float* dY, int64_t ldy,
+                                 const float* act_out, int64_t ld_act, const float* stats,
+                                 const float* ln_gamma, int64_t n_rows, int32_t d, int32_t act,
+                                 float slope, int32_t layer_norm, float out_scale, void* dZ,
+                                 bool z16, int64_t ldz, float* dgamma, float* dbeta,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  HGD_REQUIRE(d > 0 && n_rows >= 0, "%s: bad sizes", fn);
+  HGD_REQUIRE(act >= HGD_EPI_NONE && act <= HGD_EPI_RELU, "%s: bad act", fn);
+  HGD_REQUIRE(act == HGD_EPI_NONE || slope >= 0.f, "%s: activation needs slope >= 0", fn);
+  HGD_REQUIRE(layer_norm == 0 || layer_norm == 1, "%s: layer_norm 0/1", fn);
+  HGD_REQUIRE(ldy >= d && ldz >= d, "%s: ldy/ldz < d", fn);
   const bool need_a = layer_norm || act != HGD_EPI_NONE;
   if (n_rows == 0) {
     if (layer_norm && (dgamma || dbeta)) {
@@ -271,26 +281,28 @@ extern "C" hgd_status hgd_row_epilogue_backward(const float* dY, int64_t ldy, co
     }
     return HGD_OK;
   }
-  HGD_REQUIRE(dY && dZ, "hgd_row_epilogue_backward: null dY/dZ");
-  HGD_REQUIRE(!need_a || (act_out && ld_act >= d), "hgd_row_epilogue_backward: act_out required");
-  HGD_REQUIRE(!layer_norm || stats, "hgd_row_epilogue_backward: stats required for layer_norm");
+  HGD_REQUIRE(dY && dZ, "%s: null dY/dZ", fn);
+  HGD_REQUIRE(!need_a || (act_out && ld_act >= d), "%s: act_out required", fn);
+  HGD_REQUIRE(!layer_norm || stats, "%s: stats required for layer_norm", fn);
   auto al16 = [](const void* p, int64_t ld) {
     return p == nullptr || (reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 4 == 0);
   };
+  // a lane's four bf16 are one 8-byte store
+  const bool dz_al = z16 ? reinterpret_cast<uintptr_t>(dZ) % 8 == 0 && ldz % 4 == 0
+                         : al16(dZ, ldz);
   const bool aligned =
-      d % 4 == 0 && al16(dY, ldy) && al16(dZ, ldz) && al16(need_a ? act_out : nullptr, ld_act);
+      d % 4 == 0 && al16(dY, ldy) && dz_al && al16(need_a ? act_out : nullptr, ld_act);
   const int G = aligned ? (d / 4 >= 64 ? 64 : next_pow2(d / 4)) : (d >= 64 ? 64 : next_pow2(d));
   const int span = aligned ? 4 * G : G;
   if (layer_norm && span < d)
-    return fail(HGD_ERR_UNSUPPORTED,
-                "hgd_row_epilogue_backward: layer_norm needs d <= 256 (aligned) or <= 64");
+    return fail(HGD_ERR_UNSUPPORTED, "%s: layer_norm needs d <= 256 (aligned) or <= 64", fn);
   const bool want_gb = layer_norm && (dgamma || dbeta);
   const int64_t blocks = grid_blocks(n_rows, G);
   if (want_gb) {
     const size_t need = hgd_row_epilogue_backward_workspace_size(n_rows, d);
     if (workspace_bytes < need || !workspace)
-      return fail(HGD_ERR_WORKSPACE, "hgd_row_epilogue_backward: workspace %zu < required %zu",
-                  workspace_bytes, need);
+      return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < required %zu", fn, workspace_bytes,
+                  need);
   }
   RowEpiBwd p{};
   p.dY = dY;
@@ -315,7 +327,12 @@ extern "C" hgd_status hgd_row_epilogue_backward(const float* dY, int64_t ldy, co
   hipStream_t st = as_stream(stream);
   for (int c0 = 0; c0 < d; c0 += span) {
     p.col0 = c0;
-    hgd_status s = aligned ? launch<4>(G, p, blocks, st) : launch<1>(G, p, blocks, st);
+    hgd_status s;
+    if (z16)
+      s = aligned ? launch<4, bf16>(fn, G, p, blocks, st) : launch<1, bf16>(fn, G, p, blocks, st);
+    else
+      s = aligned ? launch<4, float>(fn, G, p, blocks, st)
+                  : launch<1, float>(fn, G, p, blocks, st);
     if (s != HGD_OK) return s;
   }
   if (want_gb) {
@@ -326,6 +343,41 @@ extern "C" hgd_status hgd_row_epilogue_backward(const float* dY, int64_t ldy, co
     if (dbeta) return sum_rows(p.part_b, blocks, d, dbeta, st);
   }
   return HGD_OK;
+}
+
+}  // namespace
+}  // namespace hgd
+
+extern "C" hgd_status hgd_row_epilogue_backward(const float* dY, int64_t ldy, const float* act_out,
+                                                int64_t ld_act, const float* stats,
+                                                const float* ln_gamma, int64_t n_rows, int32_t d,
+                                                int32_t act, float slope, int32_t layer_norm,
+                                                float out_scale, float* dZ, int64_t ldz,
+                                                float* dgamma, float* dbeta, void* workspace,
+                                                size_t workspace_bytes, void* stream) {
+  hgd::clear_error();
+  return hgd::row_epilogue_backward("hgd_row_epilogue_backward", dY, ldy, act_out, ld_act, stats,
+                                    ln_gamma, n_rows, d, act, slope, layer_norm, out_scale, dZ,
+                                    false, ldz, dgamma, dbeta, workspace, workspace_bytes, stream);
+}
+
+extern "C" hgd_status hgd_row_epilogue_backward_dt(
+    const float* dY, int64_t ldy, const float* act_out, int64_t ld_act, const float* stats,
+    const float* ln_gamma, int64_t n_rows, int32_t d, int32_t act, float slope,
+    int32_t layer_norm, float out_scale, void* dZ, int32_t dz_dtype, int64_t ldz, float* dgamma,
+    float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(dz_dtype == HGD_DT_F32 || dz_dtype == HGD_DT_BF16,
+              "hgd_row_epilogue_backward_dt: unknown dtype code (dz %d): HGD_DT_F32 or HGD_DT_BF16",
+              dz_dtype);
+  if (dz_dtype == HGD_DT_F32)
+    return hgd_row_epilogue_backward(dY, ldy, act_out, ld_act, stats, ln_gamma, n_rows, d, act,
+                                     slope, layer_norm, out_scale, static_cast<float*>(dZ), ldz,
+                                     dgamma, dbeta, workspace, workspace_bytes, stream);
+  return hgd::row_epilogue_backward("hgd_row_epilogue_backward_dt", dY, ldy, act_out, ld_act,
+                                    stats, ln_gamma, n_rows, d, act, slope, layer_norm, out_scale,
+                                    dZ, true, ldz, dgamma, dbeta, workspace, workspace_bytes,
+                                    stream);
 }
 
 extern "C" hgd_status hgd_row_epilogue_forward(const float* Z, int64_t ldz, int64_t n_rows,

@@ -329,7 +329,7 @@ def _self_attend(block, x):
 
 
 def _hgcn_ln_res_stack(incs, x, lns, slope, res, attend=None, gather_dtype=None,
-                       hop=two_hop_fused):
+                       hop=two_hop_fused, grad_dtype=None):
     """``lns[k](HGCNConv(A, x)) + res`` per layer, no activation on the last (HGNN_cp.py:403-406,
     :428-433): one fused two-hop per layer whose store applies the LeakyReLU, the LayerNorm
     and the residual; ``attend[k]`` (the UGformer blocks) first when given. ``incs`` is the
@@ -340,7 +340,9 @@ def _hgcn_ln_res_stack(incs, x, lns, slope, res, attend=None, gather_dtype=None,
     tables (functional.two_hop_fused). Every layer but the last then also returns the bf16 copy
     of its output, which the next layer gathers instead of casting its input — except after a
     UGformer block, whose output has no copy. Parameters, residuals, outputs and gradients stay
-    float32."""
+    float32. ``grad_dtype`` (the module's attribute; None, or torch.bfloat16 together with
+    ``gather_dtype``): each layer's epilogue backward stores its dZ in bfloat16 for the first
+    backward hop (functional.two_hop_fused)."""
     L = len(lns)
     # every layer reads res (and layer 0 reads x, the same table at the call sites): one n-ary
     # gradient pass instead of a chain of full-table accumulations (functional.fan)
@@ -357,7 +359,7 @@ def _hgcn_ln_res_stack(incs, x, lns, slope, res, attend=None, gather_dtype=None,
         return_x16 = gather_dtype is not None and not last
         y = hop(*incs, x, epilogue=None if last else "leaky_relu", slope=slope, norm=lns[k],
                 res1=ress[k], res1_scale=1.0, gather_dtype=gather_dtype, x16=x16,
-                return_x16=return_x16)
+                return_x16=return_x16, grad_dtype=grad_dtype)
         x, x16 = y if return_x16 else (y, None)
     return x
 
@@ -387,6 +389,8 @@ class SelfAwareEncoder(nn.Module):
         # None, or torch.bfloat16: the layers' hops gather bfloat16 tables (_hgcn_ln_res_stack);
         # set after construction, so the reference's constructor signature stays
         self.gather_dtype = None
+        # None, or torch.bfloat16 next to gather_dtype: the layers' backward stores dZ in bfloat16
+        self.grad_dtype = None
         self.hgnn_layers = nn.ModuleList()
         self.ugformer_layers = nn.ModuleList()
         self.lns = nn.ModuleList()
@@ -401,7 +405,8 @@ class SelfAwareEncoder(nn.Module):
         attend = self.ugformer_layers if self.use_self_att else None
         ego_embeddings = _hgcn_ln_res_stack((inc,), ego_embeddings, list(self.lns), self.leaky,
                                             ego_embeddings, attend,
-                                            getattr(self, "gather_dtype", None))
+                                            getattr(self, "gather_dtype", None),
+                                            grad_dtype=getattr(self, "grad_dtype", None))
         nu = self.data.n_users
         return split_rows(ego_embeddings, nu)
 
@@ -418,6 +423,7 @@ class RelationalAwareEncoder(nn.Module):
         self.dropout = dropout
         self.n_layers = n_layers
         self.gather_dtype = None  # or torch.bfloat16, set after construction (SelfAwareEncoder)
+        self.grad_dtype = None  # or torch.bfloat16 next to gather_dtype (SelfAwareEncoder)
         self.act = nn.LeakyReLU(self.leaky)
         self.convs = nn.ModuleList()
         self.lns = nn.ModuleList()
@@ -428,7 +434,8 @@ class RelationalAwareEncoder(nn.Module):
     def forward(self, embs, sparse_adj, att_adj=None):
         return _hgcn_ln_res_stack((incidence_of(sparse_adj),), embs, list(self.lns),
                                   float(self.leaky), embs,
-                                  gather_dtype=getattr(self, "gather_dtype", None))
+                                  gather_dtype=getattr(self, "gather_dtype", None),
+                                  grad_dtype=getattr(self, "grad_dtype", None))
 
 
 class KHGRecRelationalAwareEncoder(nn.Module):
@@ -446,6 +453,7 @@ class KHGRecRelationalAwareEncoder(nn.Module):
         self.dropout = dropout
         self.n_layers = n_layers
         self.gather_dtype = None  # or torch.bfloat16, set after construction (SelfAwareEncoder)
+        self.grad_dtype = None  # or torch.bfloat16 next to gather_dtype (SelfAwareEncoder)
         self.convs = nn.ModuleList()
         self.lns = nn.ModuleList()
         for _ in range(n_layers):
@@ -457,7 +465,8 @@ class KHGRecRelationalAwareEncoder(nn.Module):
         att = incidence_of(att_adj, cache=False)
         return _hgcn_ln_res_stack((att, inc), embs, list(self.lns), float(self.leaky), embs,
                                   gather_dtype=getattr(self, "gather_dtype", None),
-                                  hop=att_two_hop_fused)
+                                  hop=att_two_hop_fused,
+                                  grad_dtype=getattr(self, "grad_dtype", None))
 
 
 class SelfAwareEncoderHD(nn.Module):

@@ -261,12 +261,14 @@ def _row_epilogue_forward(Z: torch.Tensor, ex, Y: torch.Tensor) -> None:
         nat.stream_handle(Z.device)), "hgd_row_epilogue_forward")
 
 
-def _row_epilogue_backward(ctx, dY: torch.Tensor, need_dz: bool):
+def _row_epilogue_backward(ctx, dY: torch.Tensor, need_dz: bool, grad16: bool = False):
     """``dZ, dz_scale, dgamma, dbeta, dres1, dres2`` from a contiguous ``dY``. The gradient of
     Z is ``dz_scale·dZ``: 1 wherever hgd_row_epilogue_backward ran, which is only when dZ
     (``need_dz``), dγ or dβ is needed; a pure blend (no LayerNorm, no activation) launches
     nothing and hands back ``dY`` with the pending factor ``out_scale``, which the operator
-    applies where it is cheapest for it."""
+    applies where it is cheapest for it. ``grad16`` (a caller's ``grad_dtype``): where the
+    kernel runs it stores dZ in bfloat16 (hgd_row_epilogue_backward_dt; dγ and dβ are the fp32
+    call's bits); the pure blend's ``dY`` stays float32, no cast pass is added for it."""
     epi, slope, ln, eps, out_scale, s1, s2 = ctx.cfg
     A, stats, gamma = ctx.saved_tensors
     n, d = dY.shape
@@ -283,12 +285,18 @@ def _row_epilogue_backward(ctx, dY: torch.Tensor, need_dz: bool):
         lib = nat.load()
         wsb = lib.hgd_row_epilogue_backward_workspace_size(n, d) if (want_g or want_b) else 0
         ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev) if wsb else None
-        dZ = torch.empty_like(dY)
-        nat.check(lib.hgd_row_epilogue_backward(
-            dY.data_ptr(), dY.stride(0), nat.ptr(A), 0 if A is None else A.stride(0),
-            nat.ptr(stats), nat.ptr(gamma), n, d, epi, slope, int(ln), out_scale,
-            dZ.data_ptr(), dZ.stride(0), nat.ptr(dgamma), nat.ptr(dbeta), nat.ptr(ws), wsb,
-            nat.stream_handle(dev)), "hgd_row_epilogue_backward")
+        head = (dY.data_ptr(), dY.stride(0), nat.ptr(A), 0 if A is None else A.stride(0),
+                nat.ptr(stats), nat.ptr(gamma), n, d, epi, slope, int(ln), out_scale)
+        tail = (nat.ptr(dgamma), nat.ptr(dbeta), nat.ptr(ws), wsb, nat.stream_handle(dev))
+        if grad16:
+            dZ = torch.empty((n, d), dtype=torch.bfloat16, device=dev)
+            nat.check(lib.hgd_row_epilogue_backward_dt(
+                *head, dZ.data_ptr(), nat.DT_BF16, dZ.stride(0), *tail),
+                "hgd_row_epilogue_backward_dt")
+        else:
+            dZ = torch.empty_like(dY)
+            nat.check(lib.hgd_row_epilogue_backward(*head, dZ.data_ptr(), dZ.stride(0), *tail),
+                      "hgd_row_epilogue_backward")
     return dZ, dz_scale, dgamma, dbeta, _res_grad(ctx, dY, 0, s1), _res_grad(ctx, dY, 1, s2)
 
 
@@ -339,18 +347,20 @@ class _FusedTwoHop(torch.autograd.Function):
     ``gather16`` (the caller's ``gather_dtype``): both hops gather bfloat16 tables — bf16(X) or
     the caller's ``x16``, and the intermediate M stored in bf16 (as :func:`two_hop` stores it
     for a bf16 X) — into a float32 Y (:func:`_fused_store16`). Backward: the epilogue's gradient
-    in fp32 as without it, then dM stored in bf16 and dX in fp32."""
+    in fp32 as without it, then dM stored in bf16 and dX in fp32. ``grad16`` (the caller's
+    ``grad_dtype``, with ``gather16`` only): that gradient is stored in bf16 where its kernel
+    runs (:func:`_row_epilogue_backward`), and the first backward hop gathers it."""
 
     @staticmethod
     def forward(ctx, X, gamma, beta, res1, res2, inc: Incidence, scales, cfg, gather16: bool,
-                x16, return_x16: bool):
+                x16, return_x16: bool, grad16: bool = False):
         P, Q, R = scales
         M = spmm_csr(inc.csc, _table16(X, x16) if gather16 else X.contiguous(),
                      val=inc.edge_values("csc", R), row_scale=inc.scale("col", Q),
                      src_scale=inc.edge_src_scale("csc", R))
         ex = _row_epilogue_setup(ctx, inc.n_rows, X.shape[1], X.device, gamma, beta, res1, res2,
                                  cfg)
-        ctx.inc, ctx.scales, ctx.gather16 = inc, scales, gather16
+        ctx.inc, ctx.scales, ctx.gather16, ctx.grad16 = inc, scales, gather16, grad16
         if gather16:
             return _fused_store16(ctx, inc.csr, M, inc.val, inc.scale("row", P), ex(), return_x16)
         return spmm_csr(inc.csr, M, val=inc.val, row_scale=inc.scale("row", P), ex=ex())
@@ -361,7 +371,7 @@ class _FusedTwoHop(torch.autograd.Function):
         P, Q, R = ctx.scales
         need_dx = ctx.needs_input_grad[0]
         dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
-            ctx, dY.contiguous(), need_dx)
+            ctx, dY.contiguous(), need_dx, ctx.grad16)
         dX = None
         if need_dx:
             q = inc.scale("col", Q)
@@ -376,7 +386,7 @@ class _FusedTwoHop(torch.autograd.Function):
                           src_scale=inc.edge_src_scale("csc", P))
             dX = spmm_csr(inc.csr, dM, val=inc.val, row_scale=inc.scale("row", R),
                           out_dtype=torch.float32 if g16 else None)
-        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None, None
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None, None, None
 
 
 def _gather16(what: str, gather_dtype, X: torch.Tensor, x16, return_x16: bool) -> bool:
@@ -399,6 +409,19 @@ def _gather16(what: str, gather_dtype, X: torch.Tensor, x16, return_x16: bool) -
     return True
 
 
+def _grad16(what: str, grad_dtype, gather16: bool) -> bool:
+    """Whether the operator ``what`` stores the fused row epilogue's gradient dZ in bfloat16
+    (``grad_dtype``: None or torch.bfloat16, asked for by the caller): it goes with the bfloat16
+    gathers of ``gather_dtype``, whose backward hops read such a table."""
+    if grad_dtype is None:
+        return False
+    if grad_dtype != torch.bfloat16:
+        raise TypeError(f"{what}: grad_dtype must be None or torch.bfloat16, got {grad_dtype}")
+    if not gather16:
+        raise ValueError(f"{what}: grad_dtype goes with gather_dtype=torch.bfloat16")
+    return True
+
+
 def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
                   Q: Optional[str] = None, R: Optional[str] = None,
                   epilogue: Optional[str] = None, slope: float = 0.0,
@@ -406,7 +429,8 @@ def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
                   res1: Optional[torch.Tensor] = None, res1_scale: float = 1.0,
                   res2: Optional[torch.Tensor] = None, res2_scale: float = 1.0,
                   gather_dtype: Optional[torch.dtype] = None,
-                  x16: Optional[torch.Tensor] = None, return_x16: bool = False):
+                  x16: Optional[torch.Tensor] = None, return_x16: bool = False,
+                  grad_dtype: Optional[torch.dtype] = None):
     """``out_scale·norm(epi(P·A·Q·Aᵀ·R·X)) + res1_scale·res1 + res2_scale·res2`` with autograd.
 
     One fused hgd_spmm_fused store replaces the reference's separate LayerNorm, residual add and
@@ -422,8 +446,18 @@ def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
     store does hold) run the hops over ``X.bfloat16()`` and then the separate device ops.
     ``x16`` is the caller's own ``X.bfloat16()`` (saves the cast); ``return_x16`` returns
     ``(Y, Y16)`` with ``Y16 = bf16(Y)`` written by the same store, non-differentiable — the
-    ``x16`` of a next layer."""
+    ``x16`` of a next layer.
+
+    ``grad_dtype=torch.bfloat16`` (opt-in, only together with ``gather_dtype=torch.bfloat16``):
+    the epilogue's backward stores dZ in bfloat16 (hgd_row_epilogue_backward_dt: fp32
+    arithmetic, one rounding in the store), so the first backward hop gathers a 16-bit table like
+    every other hop of the layer. dγ, dβ and the residual gradients are untouched by it, dM
+    stays bfloat16 and dX float32; the forward is the same. Where the epilogue's backward kernel
+    does not run, the backward is ``gather_dtype``'s own, bit for bit: the pure blend (no
+    LayerNorm, no activation; dZ is dY and no cast pass is added for it) and the shapes the fused
+    store cannot hold, which take the separate device ops."""
     gather16 = _gather16("two_hop_fused", gather_dtype, X, x16, return_x16)
+    grad16 = _grad16("two_hop_fused", grad_dtype, gather16)
     for t in (X, res1, res2):
         if t is not None and t.dtype != torch.float32:
             raise TypeError(f"two_hop_fused: float32 only (the fused row epilogue has no 16-bit "
@@ -433,7 +467,7 @@ def two_hop_fused(inc: Incidence, X: torch.Tensor, P: Optional[str] = None,
         res1_scale, res2, res2_scale, gather16)
     if fusable:
         return _FusedTwoHop.apply(X, gamma, beta, res1, res2, inc, (P, Q, R), cfg, gather16, x16,
-                                  bool(return_x16))
+                                  bool(return_x16), grad16)
     if gather16:
         y = two_hop(inc, X.bfloat16(), P=P, Q=Q, R=R, epilogue=epilogue, slope=slope,
                     out_dtype=torch.float32)
@@ -509,11 +543,11 @@ class _FusedAttTwoHop(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, gamma, beta, res1, res2, att: Incidence, inc: Incidence, cfg,
-                gather16: bool, x16, return_x16: bool):
+                gather16: bool, x16, return_x16: bool, grad16: bool = False):
         Z = _att_hops(att, inc, _table16(X, x16) if gather16 else X.contiguous())
         ex = _row_epilogue_setup(ctx, att.n_rows, X.shape[1], X.device, gamma, beta, res1, res2,
                                  cfg)
-        ctx.att, ctx.inc, ctx.gather16 = att, inc, gather16
+        ctx.att, ctx.inc, ctx.gather16, ctx.grad16 = att, inc, gather16, grad16
         if gather16:
             return _fused_store16(ctx, att.csr, Z, att.val, None, ex(), return_x16)
         return spmm_csr(att.csr, Z, val=att.val, ex=ex())
@@ -522,13 +556,13 @@ class _FusedAttTwoHop(torch.autograd.Function):
     def backward(ctx, dY, _dY16=None):
         need_dx = ctx.needs_input_grad[0]
         dZ, dz_scale, dgamma, dbeta, dres1, dres2 = _row_epilogue_backward(
-            ctx, dY.contiguous(), need_dx)
+            ctx, dY.contiguous(), need_dx, ctx.grad16)
         dX = None
         if need_dx:
             if dz_scale != 1.0:  # a pure blend
                 dZ = dZ * dz_scale
             dX = _att_grad(ctx.att, ctx.inc, dZ, ctx.gather16)
-        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None, None
+        return dX, dgamma, dbeta, dres1, dres2, None, None, None, None, None, None, None
 
 
 def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
@@ -538,7 +572,8 @@ def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
                       res2: Optional[torch.Tensor] = None,
                       res2_scale: float = 1.0,
                       gather_dtype: Optional[torch.dtype] = None,
-                      x16: Optional[torch.Tensor] = None, return_x16: bool = False):
+                      x16: Optional[torch.Tensor] = None, return_x16: bool = False,
+                      grad_dtype: Optional[torch.dtype] = None):
     """``out_scale·norm(epi(att·K·Kᵀ·attᵀ·X)) + res1_scale·res1 + res2_scale·res2`` with
     autograd: :func:`att_two_hop` with the last hop's store running the fused row epilogue, as
     :func:`two_hop_fused` does for the bare two-hop (one layer of KHGRec's
@@ -551,8 +586,14 @@ def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
     four hops gather bfloat16 tables (bf16(X), T, M and Z are stored in bf16; three new
     roundings before the fused store, three in the backward chain), everything a caller sees
     stays float32. LayerNorm rows the bf16 fused store cannot hold (d > 64 with d % 8 != 0, as
-    well as d > 256) take the four bf16 hops and then the separate device ops."""
+    well as d > 256) take the four bf16 hops and then the separate device ops.
+
+    ``grad_dtype=torch.bfloat16`` as in :func:`two_hop_fused`: the epilogue's backward stores dZ
+    in bfloat16 and the first of the four backward hops gathers that table. The pure blend and
+    the shapes the fused store cannot hold keep ``gather_dtype``'s own backward, bit for bit (no
+    cast pass)."""
     gather16 = _gather16("att_two_hop_fused", gather_dtype, X, x16, return_x16)
+    grad16 = _grad16("att_two_hop_fused", grad_dtype, gather16)
     _check_att(att, inc, X, "att_two_hop_fused")
     for t in (res1, res2):
         if t is not None and t.dtype != torch.float32:
@@ -562,7 +603,7 @@ def att_two_hop_fused(att: Incidence, inc: Incidence, X: torch.Tensor,
         res1_scale, res2, res2_scale, gather16)
     if fusable:
         return _FusedAttTwoHop.apply(X, gamma, beta, res1, res2, att, inc, cfg, gather16, x16,
-                                     bool(return_x16))
+                                     bool(return_x16), grad16)
     y = _AttTwoHop.apply(X, att, inc, _EPI[epilogue], float(slope), gather16)
     return _row_epilogue_unfused(y, norm, out_scale, res1, res1_scale, res2, res2_scale,
                                  return_x16)

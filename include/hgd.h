@@ -15,6 +15,8 @@
  *   hgd_spmm_dt              the same hops over bfloat16 tables (X and / or Y in 16 bits, fp32 sums)
  *   hgd_spmm_fused_dt        hgd_spmm_fused (the hop with the LayerNorm / residual row epilogue in
  *                            its store) gathering from a bfloat16 table
+ *   hgd_row_epilogue_backward_dt  that epilogue's backward with dZ stored in bfloat16, for
+ *                            backward hops that gather 16-bit tables
  *   hgd_spmm_blocked         the same torch.sparse.mm(adj.t(), X) hop for a gathered table larger
  *                            than the Infinity Cache (source-blocked; hgd_spmm_col_blocks builds
  *                            its block-major copy of the CSC)
@@ -52,8 +54,8 @@
  *     on the calling thread. No C++ exception crosses the ABI.
  *   - Indices: row pointers are int64, column/row indices are int32 (rows, cols < 2^31).
  *   - Floating point is fp32 in and out (hgd_spmm_dt / hgd_spmm_masked_dt / hgd_spmm_blocked_dt /
- *     hgd_spmm_fused_dt / hgd_spmm_masked_fused_dt also take bfloat16 tables); sums run in fp32 in
- *     edge order (deterministic).
+ *     hgd_spmm_fused_dt / hgd_spmm_masked_fused_dt also take bfloat16 tables, and
+ *     hgd_row_epilogue_backward_dt writes one); sums run in fp32 in edge order (deterministic).
  */
 #ifndef HGD_H
 #define HGD_H
@@ -614,6 +616,29 @@ hgd_status hgd_row_epilogue_backward(const float* dY, int64_t ldy, const float* 
                                      int32_t layer_norm, float out_scale, float* dZ, int64_t ldz,
                                      float* dgamma, float* dbeta, void* workspace,
                                      size_t workspace_bytes, void* stream);
+
+/* hgd_row_epilogue_backward with the element type of dZ chosen by the caller (dz_dtype:
+ * HGD_DT_F32 or HGD_DT_BF16; ldz counts elements of that type). It serves the call sites
+ * hgd_row_epilogue_backward serves (the LayerNorm, add / blend and LeakyReLU backwards of
+ * model/layers/EquivSetConv.py:86-107 and of the layers listed at hgd_spmm_fused_dt) when the
+ * backward hops gather 16-bit tables: the first of them reads nnz·2d bytes of dZ instead of nnz·4d,
+ * and no cast pass runs over the table.
+ *   HGD_DT_BF16: the arithmetic is hgd_row_epilogue_backward's, in fp32 throughout; each element
+ *   of dZ is rounded to nearest even once, in the store, so dZ is bitwise the bfloat16 cast of the
+ *   fp32 entry point's dZ. dgamma / dbeta are summed from the unrounded values and are bitwise the
+ *   fp32 entry point's. The 16-byte path (four columns per lane, an 8-byte store of dZ) needs dZ
+ *   aligned to 8 bytes and ldz % 4 == 0 next to the fp32 tables' 16-byte test; otherwise a lane
+ *   owns one column. layer_norm needs d <= 256 on the 16-byte path, d <= 64 otherwise.
+ *   HGD_DT_F32 forwards to hgd_row_epilogue_backward (bitwise its result; its errors carry its
+ *   name). Any other code is HGD_ERR_INVALID_ARG.
+ * Workspace: hgd_row_epilogue_backward_workspace_size, unchanged. */
+hgd_status hgd_row_epilogue_backward_dt(const float* dY, int64_t ldy, const float* act_out,
+                                        int64_t ld_act, const float* stats, const float* ln_gamma,
+                                        int64_t n_rows, int32_t d, int32_t act, float slope,
+                                        int32_t layer_norm, float out_scale, void* dZ,
+                                        int32_t dz_dtype, int64_t ldz, float* dgamma,
+                                        float* dbeta, void* workspace, size_t workspace_bytes,
+                                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Skinny Linear layers on the f32 MFMA: nn.Linear(in, out) over

@@ -15,7 +15,13 @@ All variants run interleaved in ONE call, --rounds rounds of --reps event-timed 
 JSON line per variant with the median of the rounds' medians and the rounds' range, then one line
 per encoder with the deviation of the bf16 output and gradients from the fp32 ones over the same
 structure: the largest row error relative to that row's largest fp32 magnitude, and the relative
-Frobenius distance of the whole table."""
+Frobenius distance of the whole table.
+
+``--grad-dtype bf16`` adds a third timed variant per encoder next to those two, ``…_bf16_dz``:
+``gather_dtype`` and ``grad_dtype`` both bfloat16, so each layer's epilogue backward stores dZ in
+bfloat16 (hgd_row_epilogue_backward_dt) and the first backward hop gathers 2·d bytes per nonzero
+too; and a second deviation line per encoder for it. The ``…_bf16`` variant of the same run is
+its baseline. Without the option the output is unchanged."""
 import argparse
 import json
 import os
@@ -42,6 +48,8 @@ def main():
     ap.add_argument("--kg-layers", type=int, default=2)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--grad-dtype", choices=["bf16"], default=None,
+                    help="also time gather_dtype + grad_dtype = bfloat16 (a bf16 dZ)")
     args = ap.parse_args()
     import numpy as np
     import scipy.sparse as sp
@@ -57,7 +65,8 @@ def main():
         raise SystemExit("bench_fused_bf16: needs a GPU; nothing is measured without one")
     dev = torch.device("cuda")
     BF16 = torch.bfloat16
-    cases = {}  # name -> (step(gather_dtype, seed=None) -> [output, gradients...], shape info)
+    # name -> (step(gather_dtype, seed=None, grad_dtype=None) -> [output, gradients...], shape info)
+    cases = {}
 
     # ---- SelfAwareEncoder at the Yelp shape --------------------------------------------------
     nu, ni, L = args.users, args.items, args.layers
@@ -73,10 +82,10 @@ def main():
         dY = torch.randn(nu + ni, d, device=dev)
         enc = SelfAwareEncoder(data, d, d, L, 0.1, 0.1, device=dev, use_self_att=False).train()
 
-        def step(gather_dtype, seed=None, enc=enc, ego=ego, dY=dY):
+        def step(gather_dtype, seed=None, grad_dtype=None, enc=enc, ego=ego, dY=dY):
             if seed is not None:
                 torch.manual_seed(seed)  # fixes the dropped edges
-            enc.gather_dtype = gather_dtype
+            enc.gather_dtype, enc.grad_dtype = gather_dtype, grad_dtype
             ue, ie = enc(ego, dropper(adj, 0.5))
             torch.autograd.backward([ue, ie], [dY[:nu], dY[nu:]])
             out = [torch.cat([ue, ie]).detach(), ego.grad] + [p.grad for p in enc.parameters()
@@ -105,8 +114,8 @@ def main():
     kenc = KHGRecRelationalAwareEncoder(0.2, 0.1, KL, d).to(dev).train()
     att = KGAttentionPattern(h, t, r, n, nr, validate=False).update(kego, trans_M, relation_emb)
 
-    def kstep(gather_dtype, seed=None):
-        kenc.gather_dtype = gather_dtype
+    def kstep(gather_dtype, seed=None, grad_dtype=None):
+        kenc.gather_dtype, kenc.grad_dtype = gather_dtype, grad_dtype
         y = kenc(kego, kg_adj, att)
         y.backward(kdY)
         out = [y.detach(), kego.grad] + [p.grad for p in kenc.parameters()]
@@ -117,27 +126,31 @@ def main():
 
     cases["khgrec"] = (kstep, dict(entities=n, kg_nnz=len(ku), batch=B, d=d, layers=KL))
 
-    variants = [(f"{name}_{tag}", step, dt, info) for name, (step, info) in cases.items()
-                for tag, dt in (("f32", None), ("bf16", BF16))]
-    for _, step, dt, _ in variants:  # warm every shape
+    tags = [("f32", None, None), ("bf16", BF16, None)]
+    if args.grad_dtype:
+        tags.append(("bf16_dz", BF16, BF16))
+    variants = [(f"{name}_{tag}", step, dt, gd, info) for name, (step, info) in cases.items()
+                for tag, dt, gd in tags]
+    for _, step, dt, gd, _ in variants:  # warm every shape
         for _ in range(3):
-            step(dt)
+            step(dt, grad_dtype=gd)
     torch.cuda.synchronize()
-    rounds = {name: [] for name, _, _, _ in variants}
+    rounds = {name: [] for name, _, _, _, _ in variants}
     for _ in range(args.rounds):
-        for name, step, dt, _ in variants:
+        for name, step, dt, gd, _ in variants:
             ts = []
             for _ in range(args.reps):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                step(dt)
+                step(dt, grad_dtype=gd)
                 e1.record()
                 e1.synchronize()
                 ts.append(e0.elapsed_time(e1))
             rounds[name].append(statistics.median(ts))
-    for name, _, dt, info in variants:
+    for name, _, dt, gd, info in variants:
         ms = rounds[name]
-        print(json.dumps({"variant": name, "gather_dtype": "bfloat16" if dt else None,
+        opt = {"grad_dtype": "bfloat16" if gd else None} if args.grad_dtype else {}
+        print(json.dumps({"variant": name, "gather_dtype": "bfloat16" if dt else None, **opt,
                           "ms_fwd_bwd": round(statistics.median(ms), 4),
                           "ms_min_round": round(min(ms), 4), "ms_max_round": round(max(ms), 4),
                           "rounds": args.rounds, "reps": args.reps, **info}), flush=True)
@@ -159,6 +172,15 @@ def main():
                           "bf16_vs_f32_max_row": {k: float(f"{v[0]:.3e}") for k, v in devs.items()},
                           "bf16_vs_f32_fro": {k: float(f"{v[1]:.3e}") for k, v in devs.items()},
                           **info}), flush=True)
+        if args.grad_dtype:
+            dz = [x.clone() for x in step(BF16, seed=7, grad_dtype=BF16)]
+            devs = {k: row_dev(a, b) for k, a, b in zip(names, dz, f32)}
+            print(json.dumps({"deviation": name + "_bf16_dz",
+                              "bf16_dz_vs_f32_max_row": {k: float(f"{v[0]:.3e}")
+                                                         for k, v in devs.items()},
+                              "bf16_dz_vs_f32_fro": {k: float(f"{v[1]:.3e}")
+                                                     for k, v in devs.items()},
+                              **info}), flush=True)
 
 
 if __name__ == "__main__":
