@@ -409,6 +409,11 @@ _SIGNATURES = {
                                 c_void_p]),
     "hgd_topk_rows": (c_i32, [c_void_p, c_i64, c_i64, c_i64, c_i32, c_void_p, c_void_p,
                               c_void_p]),
+    "hgd_rank_topk_geometry": (None, [ctypes.POINTER(c_i32)] * 3),
+    "hgd_rank_topk_workspace_size": (c_size, [c_i64, c_i64, c_i32, c_i32]),
+    "hgd_rank_topk": (c_i32, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_i64,
+                              c_void_p, c_void_p, c_f32, c_i32, c_i32, c_void_p, c_void_p,
+                              c_void_p, c_size, c_void_p]),
     "hgd_rank_metrics": (c_i32, [c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p,
                                  ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p, c_void_p,
                                  c_void_p]),

@@ -21,10 +21,10 @@
 //   2. bitonic sort of the K candidates and of the K seeds in LDS, merge, write K ids/scores.
 // Masking is a separate scatter (hgd_mask_scores) that writes the reference's -10e8 in place.
 #include "hgd_internal.h"
+#include "topk_common.h"
 
 namespace hgd {
 
-constexpr int kTopkBlock = 256;
 constexpr int kTopkMax = 256;  // K <= 256 (the reference's item_ranking tops out at 40)
 
 __device__ __forceinline__ uint32_t float_key(float f) {
@@ -50,39 +50,6 @@ __device__ __forceinline__ int block_excl_prefix(bool flag, int* s_warp, int& to
   }
   __syncthreads();
   return base + in_wave;
-}
-
-struct Cand {
-  float s;
-  int32_t i;
-  int32_t seed;  // 1 = seed copy (precedes stream entries of equal score)
-};
-
-// a before b in the output order
-__device__ __forceinline__ bool cand_before(const Cand& a, const Cand& b) {
-  if (a.s != b.s) return a.s > b.s;
-  if (a.seed != b.seed) return a.seed > b.seed;
-  return a.i < b.i;
-}
-
-// In-LDS bitonic sort of n (power of two, <= 2*kTopkBlock) candidates, best first.
-__device__ __forceinline__ void bitonic_sort(Cand* c, int n) {
-  for (int size = 2; size <= n; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < n / 2; t += kTopkBlock) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool asc = (lo & size) == 0;  // "ascending" = best first in this sub-sequence
-        const bool swap = asc ? cand_before(c[hi], c[lo]) : cand_before(c[lo], c[hi]);
-        if (swap) {
-          const Cand tmp = c[lo];
-          c[lo] = c[hi];
-          c[hi] = tmp;
-        }
-      }
-      __syncthreads();
-    }
-  }
 }
 
 // Generic path (any score distribution): 4 radix passes over the row for the k-th largest key,

@@ -6,7 +6,9 @@ rated items set to -10e8, then numba ``find_k_largest`` (util/algorithm.py:143-1
 are scored in batches with one library GEMM (rocBLAS via torch.mm), the rated items are masked
 by ``hgd_mask_scores`` and the lists come from ``hgd_topk_rows``, which reproduces
 find_k_largest's ordering exactly — including its duplicated entries for top items among the
-first K candidates. Only the [n_users, K] result crosses to the host.
+first K candidates. Only the [n_users, K] result crosses to the host. ``fused=True`` ranks with
+``hgd_rank_topk`` instead: one kernel from the two tables and the rated-items CSR to the lists,
+with no score matrix (opt-in).
 """
 from __future__ import annotations
 
@@ -60,16 +62,86 @@ def mask_scores(scores: torch.Tensor, rated: CSR, users: torch.Tensor,
 
 
 SCORE_BUFFER_BYTES = 4 << 30  # default user batch: as many score rows as fit in 4 GiB
+RANK_MAX_K, RANK_MAX_D = 64, 256  # HGD_RANK_MAX_K / HGD_RANK_MAX_D (include/hgd.h)
+FUSED_BATCH = 1 << 16  # default rows per hgd_rank_topk launch (bounds the workspace)
+
+
+def _check_table(name: str, t: torch.Tensor) -> None:
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        raise TypeError(f"rank_users(fused=True): {name} must be a 2-D float32 device tensor")
+
+
+@torch.no_grad()
+def rank_users_fused(user_emb: torch.Tensor, item_emb: torch.Tensor, users: torch.Tensor,
+                     rated: Optional[CSR], k: int, batch: Optional[int] = None,
+                     segments: Optional[int] = None,
+                     value: float = MASK_VALUE) -> Tuple[torch.Tensor, torch.Tensor]:
+    """hgd_rank_topk: the lists of :func:`rank_users` without a score matrix. The scores are the
+    kernel's own fp32 products (f32 MFMA), so they can differ from the library GEMM's in the last
+    bits; ``batch`` only bounds the rows per launch and ``segments`` (None = by shape) only the
+    split of the catalogue over workgroups — the result depends on neither."""
+    _check_table("user_emb", user_emb)
+    _check_table("item_emb", item_emb)
+    k = int(k)
+    n_items, d = int(item_emb.shape[0]), int(item_emb.shape[1])
+    if user_emb.shape[1] != d:
+        raise ValueError(f"rank_users(fused=True): widths {user_emb.shape[1]} and {d} differ")
+    if k > RANK_MAX_K:
+        raise ValueError(f"rank_users(fused=True): k = {k} exceeds HGD_RANK_MAX_K = {RANK_MAX_K}")
+    if d > RANK_MAX_D:
+        raise ValueError(f"rank_users(fused=True): d = {d} exceeds HGD_RANK_MAX_D = {RANK_MAX_D}")
+    if k < 1 or k > n_items:
+        raise ValueError(f"rank_users(fused=True): k = {k} of {n_items} items")
+    nseg = 0 if segments is None else int(segments)
+    if nseg < 0:
+        raise ValueError("rank_users(fused=True): segments must be >= 0")
+    for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
+        if t.device.type != "cuda":  # no CPU path (DESIGN §2)
+            raise TypeError(f"rank_users(fused=True): {name} must be a 2-D float32 device "
+                            "tensor (it is on the host)")
+    if user_emb.stride(1) != 1:
+        user_emb = user_emb.contiguous()
+    if item_emb.stride(1) != 1:
+        item_emb = item_emb.contiguous()
+    dev = user_emb.device
+    users = users.to(device=dev, dtype=torch.int32).contiguous()
+    n = users.numel()
+    out_ids = torch.empty((n, k), dtype=torch.int32, device=dev)
+    out_sc = torch.empty((n, k), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out_ids, out_sc
+    rowptr = cols = None
+    if rated is not None:
+        rowptr, cols = rated.rowptr, rated.ascending_col()
+    step = max(1, int(batch)) if batch is not None else FUSED_BATCH
+    lib = nat.load()
+    ws = torch.empty(max(1, lib.hgd_rank_topk_workspace_size(min(step, n), n_items, k, nseg)),
+                     dtype=torch.uint8, device=dev)
+    for b0 in range(0, n, step):
+        rows = min(step, n - b0)
+        nat.check(lib.hgd_rank_topk(
+            user_emb.data_ptr(), user_emb.stride(0), item_emb.data_ptr(), item_emb.stride(0),
+            n_items, d, users[b0:].data_ptr(), rows, nat.ptr(rowptr),
+            cols.data_ptr() if cols is not None and cols.numel() else None, float(value), k, nseg,
+            out_ids[b0:].data_ptr(), out_sc[b0:].data_ptr(), ws.data_ptr(), ws.numel(),
+            nat.stream_handle(dev)), "hgd_rank_topk")
+    return out_ids, out_sc
 
 
 @torch.no_grad()
 def rank_users(user_emb: torch.Tensor, item_emb: torch.Tensor, users: torch.Tensor, rated: CSR,
-               k: int, batch: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               k: int, batch: Optional[int] = None, fused: bool = False,
+               segments: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k (ids, scores) for each user id in ``users``: ``user_emb[u] @ item_emb.T``, rated
     items masked to -10e8, find_k_largest ordering. Returns device int32 / fp32 [len(users), k].
 
     ``batch`` users are scored per GEMM (default: a 4 GiB score buffer; the [B, d]·[d, I]
-    product writes at 1.6 TB/s for B = 4,096 and 2.4 TB/s for B = 8,192 at the Yelp shape)."""
+    product writes at 1.6 TB/s for B = 4,096 and 2.4 TB/s for B = 8,192 at the Yelp shape).
+    ``fused=True`` takes :func:`rank_users_fused` instead (one kernel from the tables to the
+    lists, no score matrix; ``segments`` is its item split): opt-in, because its scores differ
+    from the library GEMM's in the last bits."""
+    if fused:
+        return rank_users_fused(user_emb, item_emb, users, rated, k, batch, segments)
     users = users.to(device=user_emb.device, dtype=torch.int64)
     n = users.numel()
     if batch is None:
@@ -187,8 +259,8 @@ def ranking_evaluation(tests: TestLists, ids: torch.Tensor, N: Sequence[int]) ->
 def evaluate_test_users(data, user_emb: torch.Tensor, item_emb: torch.Tensor,
                         topN: Sequence[int], tests: Optional[TestLists] = None,
                         rated: Optional[CSR] = None,
-                        batch: Optional[int] = None) -> Tuple[List[str], torch.Tensor,
-                                                              torch.Tensor]:
+                        batch: Optional[int] = None,
+                        fused: bool = False) -> Tuple[List[str], torch.Tensor, torch.Tensor]:
     """GraphRecommender.test() + ranking_evaluation (base/graph_recommender.py:61-92, 130-133)
     on the device up to the per-user counts: scores, masking, find_k_largest lists and the
     metric inputs. Returns (measure strings, ids, scores); ids / scores are the device
@@ -200,12 +272,13 @@ def evaluate_test_users(data, user_emb: torch.Tensor, item_emb: torch.Tensor,
     if not tests.users:
         raise ValueError("evaluate_test_users: empty test set")
     uid = torch.tensor([data.user[u] for u in tests.users], dtype=torch.int64)
-    ids, sc = rank_users(user_emb, item_emb, uid, rated, max(int(n) for n in topN), batch)
+    ids, sc = rank_users(user_emb, item_emb, uid, rated, max(int(n) for n in topN), batch,
+                         fused=fused)
     return ranking_evaluation(tests, ids, topN), ids, sc
 
 
 def test_rec_list(data, user_emb: torch.Tensor, item_emb: torch.Tensor, max_N: int,
-                  batch: Optional[int] = None) -> Dict:
+                  batch: Optional[int] = None, fused: bool = False) -> Dict:
     """Drop-in for ``GraphRecommender.test()``: ``{user: [(item_name, score), ...]}`` over
     ``data.test_set`` in its iteration order, ready for the reference's ``evaluate()``."""
     users = list(data.test_set)
@@ -213,7 +286,7 @@ def test_rec_list(data, user_emb: torch.Tensor, item_emb: torch.Tensor, max_N: i
         return {}
     uid = torch.tensor([data.user[u] for u in users], dtype=torch.int64)
     rated = rated_csr(data.interaction_mat, user_emb.device)
-    ids, sc = rank_users(user_emb, item_emb, uid, rated, max_N, batch)
+    ids, sc = rank_users(user_emb, item_emb, uid, rated, max_N, batch, fused=fused)
     ids, sc = ids.cpu().numpy(), sc.cpu().numpy()
     rec = {}
     for r, u in enumerate(users):

@@ -95,6 +95,7 @@ class CSR:
         self._packed: Dict[Tuple[int, int, int], tuple] = {}
         self._row_order: Optional[Tuple[torch.Tensor, ...]] = None
         self._ord_vals: Dict[Tuple[int, int], tuple] = {}
+        self._col_asc: Optional[torch.Tensor] = None
         self._plan_arrays = ()
         self.plan = nat.SplitPlan()
         self.plan.threshold = 0
@@ -186,6 +187,20 @@ class CSR:
                 start.zero_()
             got = self._col_blocks[n_blocks] = (start, bcol, perm)
         return got
+
+    def ascending_col(self) -> torch.Tensor:
+        """``col`` with every row's columns ascending (duplicates kept), as the fused ranking's
+        binary search needs them: ``col`` itself when the rows are known to be ascending, else a
+        copy sorted on the device by (row, column), built once and cached."""
+        if self.cols_ascending or self.nnz == 0:
+            return self.col
+        if self._col_asc is None:
+            rows = torch.repeat_interleave(
+                torch.arange(self.n_rows, dtype=torch.int64, device=self.device),
+                self.rowptr[1:] - self.rowptr[:-1], output_size=self.nnz)
+            key = torch.sort(rows * max(1, self.n_cols) + self.col.to(torch.int64)).values
+            self._col_asc = (key % max(1, self.n_cols)).to(torch.int32)
+        return self._col_asc
 
     def blocked_values(self, n_blocks: int, val: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """``val`` (per-nonzero weights in this structure's order) gathered into the block-major

@@ -367,7 +367,11 @@ class Recommender:
 class GraphRecommender(Recommender):
     """base/graph_recommender.py:18-239 with the evaluation on the device. Plugins set
     ``self.user_emb`` / ``self.item_emb`` (device [U, d] / [I, d]) before ``test`` /
-    ``fast_evaluation``, as the reference's do for ``predict``."""
+    ``fast_evaluation``, as the reference's do for ``predict``. ``eval_fused = True`` ranks with
+    the fused score / mask / top-K kernel (``evaluation.rank_users(fused=True)``): no score
+    matrix, scores that can differ from the library GEMM's in the last bits."""
+
+    eval_fused = False
 
     def __init__(self, conf, training_set, test_set, knowledge_set, **kwargs):
         super().__init__(conf, training_set, test_set, knowledge_set, **kwargs)
@@ -408,7 +412,8 @@ class GraphRecommender(Recommender):
             self._tests = ev.TestLists(self.data.test_set, self.data.item, self.device)
             self._rated = ev.rated_csr(self.data.interaction_mat, self.device)
         return ev.evaluate_test_users(self.data, self.user_emb, self.item_emb, self.topN,
-                                      tests=self._tests, rated=self._rated)
+                                      tests=self._tests, rated=self._rated,
+                                      fused=self.eval_fused)
 
     def test(self) -> Dict:
         """{test user: [(item, score), ...max_N]} in data.test_set order (graph_recommender.py

@@ -1008,6 +1008,54 @@ hgd_status hgd_mask_scores(float* scores, int64_t n_rows, int64_t ld, const int6
 hgd_status hgd_topk_rows(const float* scores, int64_t n_rows, int64_t n_cols, int64_t ld,
                          int32_t k, int32_t* out_ids, float* out_scores, void* stream);
 
+/* Fused score, mask and top-K (GraphRecommender.test, base/graph_recommender.py:61-92, and
+ * find_k_largest, util/algorithm.py:143-173): from the two fp32 embedding tables and the
+ * rated-items CSR straight to the [n_rows, k] lists; no score is written to memory.
+ *   Row r ranks user u = users ? users[r] : r (device int32, ids of user_emb rows).
+ *   raw(u, i)  = the fp32 value the kernel's product gives for user_emb[u, :d]·item_emb[i, :d]
+ *                (f32 MFMA: exact products, fp32 sums; within 1e-5·Σ_j|u_j·v_j| of the float64
+ *                dot product).
+ *   eff(u, i)  = mask_value if i is in rated_cols[rated_rowptr[u] : rated_rowptr[u+1]], else
+ *                raw(u, i) (a rated item with a lower raw score is raised to mask_value, as
+ *                hgd_mask_scores does); rated_rowptr == NULL masks nothing.
+ *   Output: exactly what hgd_topk_rows returns for the row of effective scores — the first k of
+ *   {(c_j, j): j < k} ∪ {(c_i, i)} by score descending, seed before stream, index ascending
+ *   (seed duplicates listed; ±0.0 compare equal and the listed score keeps its sign).
+ *   out_ids int32 / out_scores fp32, dense [n_rows, k].
+ *   Position independence: a pair's raw score is one fixed instruction sequence over d (padded
+ *   with zeros), so its bits do not depend on the row r, the tile, the segment, the launch or
+ *   n_segments: a user listed twice gets identical rows, every n_segments gives identical output
+ *   and every call repeats bitwise.
+ *   rated_cols ascending within each row is a precondition (duplicates allowed); an unsorted row
+ *   may give a wrong list but never an out-of-range access. users[r] and the rated rows must be
+ *   valid indices of their tables.
+ *   Any ldu, ldi >= d and any 4-byte-aligned base are accepted; item rows that are 16-byte
+ *   aligned (base and ldi) take vector loads.
+ *   n_segments splits the item range over that many workgroups per block of users (a handful of
+ *   users still fills the chip); it is clamped to the tile count and to 256. 0 chooses from
+ *   n_rows, n_items and a constant CU count of 256 — no device query, so the choice and the
+ *   workspace size are pure functions of the arguments. The segments are merged by a second
+ *   launch: no workgroup waits for another.
+ *   No host synchronisation and no allocation: capturable.
+ *   Before the first HIP call: null tables or outputs, d < 1, k < 1, k > n_items, ld < d,
+ *   n_segments < 0, n_items >= 2^31 → HGD_ERR_INVALID_ARG; k > HGD_RANK_MAX_K, d > HGD_RANK_MAX_D
+ *   or n_rows >= 2^31 → HGD_ERR_UNSUPPORTED; a workspace shorter than
+ *   hgd_rank_topk_workspace_size (same arguments) → HGD_ERR_WORKSPACE; n_rows == 0 → HGD_OK with
+ *   nothing launched.
+ *   hgd_rank_topk_geometry (host only): the kernel's tiling, for tests and tools. */
+#define HGD_RANK_MAX_K 64
+#define HGD_RANK_MAX_D 256
+void hgd_rank_topk_geometry(int32_t* users_per_block, int32_t* items_per_tile,
+                            int32_t* candidate_slots);
+size_t hgd_rank_topk_workspace_size(int64_t n_rows, int64_t n_items, int32_t k,
+                                    int32_t n_segments);
+hgd_status hgd_rank_topk(const float* user_emb, int64_t ldu, const float* item_emb, int64_t ldi,
+                         int64_t n_items, int32_t d, const int32_t* users, int64_t n_rows,
+                         const int64_t* rated_rowptr, const int32_t* rated_cols,
+                         float mask_value, int32_t k, int32_t n_segments,
+                         int32_t* out_ids, float* out_scores,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-user inputs of ranking_evaluation (util/evaluation.py:169-196) for the lists above:
  *   hits[r, c] = |set(test items of r) ∩ set(ids[r, :N_c])|        (Metric.hits, :8-15)
  *   dcg[r, c]  = Σ_{n < N_c, ids[r, n] in test} discount[n], in n order (Metric.NDCG, :84-97)
