@@ -24,6 +24,8 @@ HGD_OK = 0
 EPI_NONE, EPI_LEAKY_RELU, EPI_RELU = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1  # HGD_DT_*: element types of hgd_spmm_dt / hgd_spmm_masked_dt
 PACKED_IDX_BITS, PACKED_MAX_DICT = 22, 1024  # HGD_SPMM_PACKED_IDX_BITS / _MAX_DICT
+ORDER_NONE, ORDER_MIN_COLUMN, ORDER_GREEDY = 0, 1, 2  # HGD_ORDER_*: how an ordered hop's rows go
+ORDER_COL_CAP = 1024  # HGD_ORDER_COL_CAP
 _STATUS_NAMES = {0: "HGD_OK", 1: "HGD_ERR_INVALID_ARG", 2: "HGD_ERR_HIP",
                  3: "HGD_ERR_UNSUPPORTED", 4: "HGD_ERR_WORKSPACE"}
 
@@ -285,6 +287,20 @@ _SIGNATURES = {
     "hgd_spmm_blocked_ordered": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                                          c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32,
                                          c_f32, c_i32, c_void_p]),
+    "hgd_row_order_greedy": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32,
+                                     c_i32, c_i32, c_void_p]),
+    "hgd_col_block_order_greedy": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_i64, c_i32,
+                                           c_i32, c_i32, c_i32, c_i32, c_void_p]),
+    "hgd_spmm_row_order_from_workspace_size": (c_size, [c_i64]),
+    "hgd_spmm_row_order_from": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "hgd_spmm_col_blocks_ordered_from_workspace_size": (c_size, [c_i64, c_i32]),
+    "hgd_spmm_col_blocks_ordered_from": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i32,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size,
+                                                 c_void_p]),
+    "hgd_spmm_order_geometry": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_i32),
+                                        ctypes.POINTER(c_i64)]),
+    "hgd_spmm_row_order_kind_for": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_i32]),
     "hgd_spmm_packed_for": (c_i32, [c_i64, c_i32, c_i64, c_i32]),
     "hgd_spmm_packed_fits": (c_i32, [c_i64, c_i32, c_i64, c_i32]),
     "hgd_spmm_pack_entries": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i32,

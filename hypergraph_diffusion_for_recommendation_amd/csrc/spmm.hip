@@ -222,6 +222,104 @@ BlockOrderWs block_order_ws(int64_t n_rows, int32_t n_blk) {
   return w;
 }
 
+// Permutation check of a caller's order (hgd_spmm_row_order_from, hgd_spmm_col_blocks_ordered_from):
+// flag[k·n_rows + order[k·n_rows + p]] = 1 for every entry inside [0, n_rows) — plain stores of the
+// same value, no atomics — so the flags sum to n = n_blk·n_rows exactly when every block's order
+// is a permutation.
+__global__ void order_flag_kernel(const int32_t* __restrict__ order, int64_t n_rows, int64_t n,
+                                  int32_t* __restrict__ flag) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = order[i];
+  if (r >= 0 && r < n_rows) flag[i - i % n_rows + r] = 1;
+}
+
+struct WidenFlag {
+  __host__ __device__ int64_t operator()(int32_t f) const { return f; }
+};
+using FlagIter = hipcub::TransformInputIterator<int64_t, WidenFlag, const int32_t*>;
+
+// what the check needs behind a builder's own workspace: the sum, then the reduction's own
+size_t order_check_ws(int64_t n) {
+  size_t red = 0;
+  if (hipcub::DeviceReduce::Sum(nullptr, red, FlagIter(nullptr, WidenFlag{}),
+                                static_cast<int64_t*>(nullptr), n) != hipSuccess)
+    return 0;
+  return 256 + align_up(red > 0 ? red : 1);
+}
+
+// Whether order [n] is n / n_rows permutations of [0, n_rows), one after the other. flag: int32 [n]
+// of scratch; tail: order_check_ws(n) bytes. Waits for the stream (the caller built the order on
+// the host: it has synchronised already), so nothing reads the structure through a bad order.
+hgd_status check_order(const char* fn, const int32_t* order, int64_t n_rows, int64_t n,
+                       int32_t* flag, char* tail, size_t tail_bytes, hipStream_t st) {
+  HGD_HIP(hipMemsetAsync(flag, 0, static_cast<size_t>(n) * sizeof(int32_t), st));
+  hipLaunchKernelGGL(order_flag_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, order, n_rows, n,
+                     flag);
+  hgd_status s = check_launch(fn, "order flags");
+  if (s != HGD_OK) return s;
+  int64_t* sum = reinterpret_cast<int64_t*>(tail);
+  size_t red_bytes = tail_bytes - 256;
+  HGD_HIP(hipcub::DeviceReduce::Sum(tail + 256, red_bytes, FlagIter(flag, WidenFlag{}), sum, n, st));
+  int64_t got = -1;
+  HGD_HIP(hipMemcpyAsync(&got, sum, sizeof(got), hipMemcpyDeviceToHost, st));
+  HGD_HIP(hipStreamSynchronize(st));
+  if (got != n)
+    return fail(HGD_ERR_INVALID_ARG, "%s: the order is not a permutation of the rows (%lld of %lld "
+                "rows named)", fn, (long long)got, (long long)n);
+  return HGD_OK;
+}
+
+// hgd_spmm_row_order's steps after its sort, over any order: permuted lengths, scan, copy of the
+// columns and their source positions. len / tail: RowOrderWs's.
+hgd_status row_order_tail(const char* fn, const int64_t* rowptr, const int32_t* col,
+                          const int32_t* order, int64_t n_rows, int64_t* rowptr_o, int32_t* col_o,
+                          int32_t* perm, int64_t* len, char* tail, size_t tail_bytes,
+                          hipStream_t st) {
+  constexpr int kRowsPerBlock = kBlock / kOrdG;
+  const int64_t grid = (n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  hipLaunchKernelGGL(row_order_len_kernel, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, st, rowptr,
+                     order, n_rows, len);
+  hgd_status s = check_launch(fn, "lengths");
+  if (s != HGD_OK) return s;
+  HGD_HIP(hipcub::DeviceScan::ExclusiveSum(tail, tail_bytes, len, rowptr_o, n_rows + 1, st));
+  hipLaunchKernelGGL(row_order_copy_kernel, dim3(grid), dim3(kBlock), 0, st, rowptr, col, order,
+                     rowptr_o, n_rows, col_o, perm);
+  return check_launch(fn, "copy");
+}
+
+// hgd_spmm_col_blocks_ordered's steps after its sorts, over any per-block orders blk_out_row:
+// permuted lengths per block, one scan, every piece's destination, the scatter. start: the natural
+// block-major starts (hgd_spmm_col_blocks' count and scan), then the destinations; cnt: scratch
+// of the same size.
+hgd_status block_order_tail(const char* fn, const int64_t* rowptr, const int32_t* col,
+                            int64_t n_rows, int64_t n_cols, int32_t n_blocks, int64_t* blk_start,
+                            int32_t* blk_col, int32_t* blk_perm, const int32_t* blk_out_row,
+                            int64_t* cnt, int64_t* start, char* tail, size_t tail_bytes,
+                            hipStream_t st) {
+  const int64_t n = static_cast<int64_t>(n_blocks) * n_rows;
+  const int64_t row_grid = (n_rows + 255) / 256;
+  hgd_status s;
+  for (int32_t k = 0; k < n_blocks; ++k) {
+    const int64_t off = static_cast<int64_t>(k) * n_rows;
+    // (writes the closing 0 at cnt[off + n_rows], which the next block's launch overwrites)
+    hipLaunchKernelGGL(row_order_len_kernel, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, st,
+                       start + off, blk_out_row + off, n_rows, cnt + off);
+    s = check_launch(fn, "lengths");
+    if (s != HGD_OK) return s;
+  }
+  HGD_HIP(hipcub::DeviceScan::ExclusiveSum(tail, tail_bytes, cnt, blk_start, n + 1, st));
+  // every piece's start in the ordered copy, indexed by (block, row), and the nonzeros moved
+  // there from the source structure: blk_perm is their source position as in hgd_spmm_col_blocks
+  hipLaunchKernelGGL(block_order_dest_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, blk_start,
+                     blk_out_row, n_rows, n, start);
+  s = check_launch(fn, "destinations");
+  if (s != HGD_OK) return s;
+  hipLaunchKernelGGL(col_block_scatter_kernel, dim3(row_grid), dim3(256), 0, st, rowptr, col,
+                     n_rows, n_cols, n_blocks, start, blk_col, blk_perm);
+  return check_launch(fn, "ordered scatter");
+}
+
 }  // namespace
 }  // namespace hgd
 
@@ -255,21 +353,73 @@ extern "C" hgd_status hgd_spmm_row_order(const int64_t* rowptr, const int32_t* c
   int64_t* len = reinterpret_cast<int64_t*>(ws + w.len);
   hipLaunchKernelGGL(row_min_key_kernel, dim3(grid), dim3(kBlock), 0, st, rowptr, col, n_rows,
                      static_cast<int32_t>(n_cols), keys);
-  hgd_status s = check_launch("hgd_spmm_row_order keys");
+  hgd_status s = check_launch("hgd_spmm_row_order", "keys");
   if (s != HGD_OK) return s;
   // stable: rows with the same smallest column stay in natural order
   s = hgd_sort_perm(keys, n_rows, n_cols + 1, keys_s, order, ws + w.tail, workspace_bytes - w.tail,
                     stream);
   if (s != HGD_OK) return s;
-  hipLaunchKernelGGL(row_order_len_kernel, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, st, rowptr,
-                     order, n_rows, len);
-  s = check_launch("hgd_spmm_row_order lengths");
+  return row_order_tail("hgd_spmm_row_order", rowptr, col, order, n_rows, rowptr_o, col_o, perm,
+                        len, ws + w.tail, workspace_bytes - w.tail, st);
+}
+
+extern "C" size_t hgd_spmm_row_order_from_workspace_size(int64_t n_rows) {
+  if (n_rows <= 0 || n_rows >= 0x7fffffffLL) return 0;
+  const size_t own = hgd::row_order_ws(n_rows).total, check = hgd::order_check_ws(n_rows);
+  return own && check ? own + check : 0;
+}
+
+extern "C" hgd_status hgd_spmm_row_order_from(const int32_t* order, const int64_t* rowptr,
+                                              const int32_t* col, int64_t n_rows, int64_t n_cols,
+                                              int64_t* rowptr_o, int32_t* col_o, int32_t* perm,
+                                              void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  using namespace hgd;
+  clear_error();
+  constexpr const char* fn = "hgd_spmm_row_order_from";
+  HGD_REQUIRE(n_rows >= 0 && n_cols >= 0, "%s: negative sizes", fn);
+  HGD_REQUIRE(n_rows < 0x7fffffffLL, "%s: n_rows >= 2^31 - 1", fn);
+  HGD_REQUIRE(n_cols < 0x7fffffffLL, "%s: n_cols >= 2^31 - 1", fn);
+  if (n_rows == 0) return HGD_OK;
+  HGD_REQUIRE(rowptr && order && rowptr_o, "%s: null rowptr / order / rowptr_o", fn);
+  const RowOrderWs w = row_order_ws(n_rows);
+  const size_t need = hgd_spmm_row_order_from_workspace_size(n_rows);
+  if (need == 0 || !workspace || workspace_bytes < need)
+    return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < %zu", fn, workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  // (the flags where the builder's keys would be; the check's own behind the builder's workspace)
+  hgd_status s = check_order(fn, order, n_rows, n_rows, reinterpret_cast<int32_t*>(ws + w.keys),
+                             ws + w.total, need - w.total, st);
   if (s != HGD_OK) return s;
-  size_t tail_bytes = workspace_bytes - w.tail;
-  HGD_HIP(hipcub::DeviceScan::ExclusiveSum(ws + w.tail, tail_bytes, len, rowptr_o, n_rows + 1, st));
-  hipLaunchKernelGGL(row_order_copy_kernel, dim3(grid), dim3(kBlock), 0, st, rowptr, col, order,
-                     rowptr_o, n_rows, col_o, perm);
-  return check_launch("hgd_spmm_row_order copy");
+  return row_order_tail(fn, rowptr, col, order, n_rows, rowptr_o, col_o, perm,
+                        reinterpret_cast<int64_t*>(ws + w.len), ws + w.tail, w.total - w.tail, st);
+}
+
+extern "C" int32_t hgd_spmm_order_geometry(int32_t d, int32_t blocked, int32_t* rows_per_wg,
+                                           int64_t* window) {
+  using namespace hgd;
+  if (d <= 0 || !rows_per_wg || !window) return 0;
+  // the fp32 hop's own pass plan over 16-byte aligned rows of d (a blocked hop: any block count)
+  SpmmRequest r{"hgd_spmm_order_geometry", nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0,
+                nullptr, d, nullptr, d, d, HGD_EPI_NONE, 0.f};
+  r.blocked = blocked != 0;
+  r.n_blk = blocked ? 2 : 0;
+  SpmmPassPlan p;
+  if (spmm_pass_plan(r, 4, 4, &p) != HGD_OK) return 0;
+  *rows_per_wg = kBlock / p.G;
+  // the gathers an XCD's 4 MiB of L2 holds: one is a pass's piece of a source row
+  const int64_t piece = static_cast<int64_t>(d < p.step ? d : p.step) * 4;
+  *window = (int64_t(4) << 20) / piece;
+  return 1;
+}
+
+extern "C" int32_t hgd_spmm_row_order_kind_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz,
+                                               int32_t d, int32_t n_blocks) {
+  // the greedy order wherever a size rule orders the hop (a blocked one: each block's rows)
+  const int32_t on = n_blocks > 1 ? hgd_spmm_block_order_for(n_rows, n_src_rows, nnz, d, n_blocks)
+                                  : hgd_spmm_row_order_for(n_rows, n_src_rows, nnz, d);
+  return on ? HGD_ORDER_GREEDY : HGD_ORDER_NONE;
 }
 
 extern "C" int32_t hgd_spmm_row_order_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz,
@@ -505,8 +655,8 @@ extern "C" hgd_status hgd_spmm_col_blocks_ordered(const int64_t* rowptr, const i
                      n_rows, n_cols, n_blocks, start, blk_col, static_cast<int32_t*>(nullptr));
   s = check_launch(fn, "scatter");
   if (s != HGD_OK) return s;
-  // hgd_spmm_row_order's pattern over each block's own CSR (start + k·n_rows, blk_col): keys,
-  // stable sort (an empty piece has the key n_cols and sorts last), permuted lengths
+  // hgd_spmm_row_order's pattern over each block's own CSR (start + k·n_rows, blk_col): keys and
+  // stable sort (an empty piece has the key n_cols and sorts last); the rest is any order's
   for (int32_t k = 0; k < n_blocks; ++k) {
     const int64_t off = static_cast<int64_t>(k) * n_rows;
     hipLaunchKernelGGL(row_min_key_kernel, dim3(key_grid), dim3(kBlock), 0, st, start + off,
@@ -516,22 +666,57 @@ extern "C" hgd_status hgd_spmm_col_blocks_ordered(const int64_t* rowptr, const i
     s = hgd_sort_perm(keys, n_rows, n_cols + 1, keys_s, blk_out_row + off, ws + w.tail, tail_bytes,
                       stream);
     if (s != HGD_OK) return s;
-    // (writes the closing 0 at cnt[off + n_rows], which the next block's launch overwrites)
-    hipLaunchKernelGGL(row_order_len_kernel, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, st,
-                       start + off, blk_out_row + off, n_rows, cnt + off);
-    s = check_launch(fn, "lengths");
-    if (s != HGD_OK) return s;
   }
-  HGD_HIP(hipcub::DeviceScan::ExclusiveSum(ws + w.tail, tail_bytes, cnt, blk_start, n + 1, st));
-  // every piece's start in the ordered copy, indexed by (block, row), and the nonzeros moved
-  // there from the source structure: blk_perm is their source position as in hgd_spmm_col_blocks
-  hipLaunchKernelGGL(block_order_dest_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, blk_start,
-                     blk_out_row, n_rows, n, start);
-  s = check_launch(fn, "destinations");
+  return block_order_tail(fn, rowptr, col, n_rows, n_cols, n_blocks, blk_start, blk_col, blk_perm,
+                          blk_out_row, cnt, start, ws + w.tail, tail_bytes, st);
+}
+
+extern "C" size_t hgd_spmm_col_blocks_ordered_from_workspace_size(int64_t n_rows,
+                                                                  int32_t n_blocks) {
+  if (n_rows <= 0 || n_rows >= 0x7fffffffLL || n_blocks <= 0 || n_blocks > 64) return 0;
+  const size_t own = hgd::block_order_ws(n_rows, n_blocks).total;
+  const size_t check = hgd::order_check_ws(static_cast<int64_t>(n_blocks) * n_rows);
+  return own && check ? own + check : 0;
+}
+
+extern "C" hgd_status hgd_spmm_col_blocks_ordered_from(const int32_t* blk_order,
+                                                       const int64_t* rowptr, const int32_t* col,
+                                                       int64_t n_rows, int64_t n_cols,
+                                                       int32_t n_blocks, int64_t* blk_start,
+                                                       int32_t* blk_col, int32_t* blk_perm,
+                                                       void* workspace, size_t workspace_bytes,
+                                                       void* stream) {
+  using namespace hgd;
+  clear_error();
+  constexpr const char* fn = "hgd_spmm_col_blocks_ordered_from";
+  HGD_REQUIRE(n_rows >= 0 && n_cols >= 0, "%s: negative sizes", fn);
+  HGD_REQUIRE(n_blocks >= 1 && n_blocks <= 64, "%s: blocks must be 1..64", fn);
+  HGD_REQUIRE(n_rows < 0x7fffffffLL, "%s: n_rows >= 2^31 - 1", fn);
+  HGD_REQUIRE(n_cols < 0x7fffffffLL, "%s: n_cols >= 2^31 - 1", fn);
+  if (n_rows == 0) return HGD_OK;
+  HGD_REQUIRE(rowptr && blk_start && blk_order, "%s: null rowptr / blk_start / blk_order", fn);
+  const BlockOrderWs w = block_order_ws(n_rows, n_blocks);
+  const size_t need = hgd_spmm_col_blocks_ordered_from_workspace_size(n_rows, n_blocks);
+  if (need == 0 || !workspace || workspace_bytes < need)
+    return fail(HGD_ERR_WORKSPACE, "%s: workspace %zu < %zu", fn, workspace_bytes, need);
+  const int64_t n = static_cast<int64_t>(n_blocks) * n_rows;
+  hipStream_t st = as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  int64_t* cnt = reinterpret_cast<int64_t*>(ws + w.cnt);
+  int64_t* start = reinterpret_cast<int64_t*>(ws + w.start);
+  // (the flags where the counts go next; the check's own behind the builder's workspace)
+  hgd_status s = check_order(fn, blk_order, n_rows, n, reinterpret_cast<int32_t*>(cnt),
+                             ws + w.total, need - w.total, st);
   if (s != HGD_OK) return s;
-  hipLaunchKernelGGL(col_block_scatter_kernel, dim3(row_grid), dim3(256), 0, st, rowptr, col,
-                     n_rows, n_cols, n_blocks, start, blk_col, blk_perm);
-  return check_launch(fn, "ordered scatter");
+  // the natural block-major starts (hgd_spmm_col_blocks' count and scan)
+  hipLaunchKernelGGL(col_block_count_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, st, rowptr,
+                     col, n_rows, n_cols, n_blocks, cnt);
+  s = check_launch(fn, "count");
+  if (s != HGD_OK) return s;
+  size_t tail_bytes = w.total - w.tail;
+  HGD_HIP(hipcub::DeviceScan::ExclusiveSum(ws + w.tail, tail_bytes, cnt, start, n + 1, st));
+  return block_order_tail(fn, rowptr, col, n_rows, n_cols, n_blocks, blk_start, blk_col, blk_perm,
+                          blk_order, cnt, start, ws + w.tail, tail_bytes, st);
 }
 
 extern "C" hgd_status hgd_spmm_blocked_ordered(const int64_t* blk_start, const int32_t* blk_col,

@@ -34,6 +34,11 @@ SPLIT_NNZ_PER_THRESHOLD = 8192
 SEGMENTED_MAX_AVG_DEGREE = 32
 # lane-group tasks needed to fill MI355X: 256 CUs × 16 waves × 4 groups of 16 lanes (d = 64)
 TARGET_GROUPS = 16384
+# the greedy row order's placement (hgd_row_order_greedy): the XCDs workgroups are dealt to
+# round-robin on MI355X, and the chunks each XCD's part is cut into (1: the best order; more bound
+# the host build)
+ORDER_XCDS = 8
+ORDER_CHUNKS_PER_XCD = 1
 
 
 def auto_split(n_rows: int, nnz: int) -> Tuple[int, int]:
@@ -67,6 +72,39 @@ def _stream(device) -> int:
     return nat.stream_handle(device)
 
 
+_ORDER_GEOM: Dict[Tuple[int, bool], Tuple[int, int, int, int]] = {}
+
+
+def order_geometry(d: int, blocked: bool) -> Tuple[int, int, int, int]:
+    """``(window, rows_per_wg, n_xcd, chunks_per_xcd)`` of the greedy order for the fp32 hop at
+    width ``d`` (``blocked``: the source-blocked hop): the first two from the launcher's own pass
+    plan (hgd_spmm_order_geometry: 16 rows a workgroup and 16,384 gathers in an XCD's L2 at
+    d = 64), the key the orders are cached under. ``HGD_SPMM_ORDER_PLACE=0`` builds the same
+    chunks as one sequence, not placed on the XCDs (a measurement switch; unset or ``1``:
+    placed)."""
+    env = os.environ.get("HGD_SPMM_ORDER_PLACE", "")
+    if env not in ("", "0", "1"):
+        raise ValueError(f"HGD_SPMM_ORDER_PLACE must be 0 or 1, got {env!r}")
+    got = _ORDER_GEOM.get((int(d), bool(blocked)))
+    if got is None:
+        rows, window = ctypes.c_int32(0), ctypes.c_int64(0)
+        if not nat.load().hgd_spmm_order_geometry(int(d), int(bool(blocked)), ctypes.byref(rows),
+                                                  ctypes.byref(window)):
+            raise ValueError(f"order_geometry: no pass plan at d = {d}")
+        got = _ORDER_GEOM[(int(d), bool(blocked))] = (int(window.value), int(rows.value))
+    if env == "0":
+        return got + (1, ORDER_XCDS * ORDER_CHUNKS_PER_XCD)
+    return got + (ORDER_XCDS, ORDER_CHUNKS_PER_XCD)
+
+
+def _need_geom(geom: Optional[tuple]) -> tuple:
+    """A greedy order is one of a geometry: there is no default width to take one from."""
+    if geom is None or len(geom) != 4:
+        raise ValueError("a greedy order needs geom = order_geometry(d, blocked) of the hop it "
+                         "is walked by")
+    return tuple(int(g) for g in geom)
+
+
 class CSR:
     """One orientation: ``rowptr`` int64 [n_rows+1], ``col`` int32 [nnz] (device tensors),
     and the long-row split plan used by :func:`spmm_csr`."""
@@ -94,6 +132,12 @@ class CSR:
         self._blk_ord_vals: Dict[Tuple[int, int], tuple] = {}
         self._packed: Dict[Tuple[int, int, int], tuple] = {}
         self._row_order: Optional[Tuple[torch.Tensor, ...]] = None
+        # the greedy orders, by (block count or 0, window, rows per workgroup, XCDs, chunks)
+        self._greedy: Dict[tuple, Tuple[torch.Tensor, ...]] = {}
+        # whether the structure outlives the steps that hop over it (Incidence.persist): only
+        # then is an order worth a build on the host. A structure made per step — an edge-dropped
+        # one, a learned hypergraph's — keeps the min-column order, built on the stream
+        self.persistent = False
         self._ord_vals: Dict[Tuple[int, int], tuple] = {}
         self._col_asc: Optional[torch.Tensor] = None
         self._plan_arrays = ()
@@ -253,12 +297,41 @@ class CSR:
             got = self._col_block_plans[n_blocks] = (plans, arrays)
         return got[0]
 
-    def col_blocks_ordered(self, n_blocks: int) -> Tuple[torch.Tensor, ...]:
+    def _greedy_order(self, n_blocks: int, geom: tuple) -> torch.Tensor:
+        """The greedy order on the device: hgd_row_order_greedy (``n_blocks`` = 0) or
+        hgd_col_block_order_greedy over a host copy of ``rowptr`` and ``col``, made for this
+        build alone — a stream synchronisation, once per structure and geometry, outside any
+        capture."""
+        window, rows_per_wg, n_xcd, chunks = geom
+        rowptr, col = self.rowptr.cpu().contiguous(), self.col.cpu().contiguous()
+        lib = nat.load()
+        out = torch.empty(max(1, n_blocks) * self.n_rows, dtype=torch.int32)
+        cp = col.data_ptr() if self.nnz else None
+        if n_blocks:
+            nat.check(lib.hgd_col_block_order_greedy(
+                rowptr.data_ptr(), cp, self.n_rows, self.n_cols, n_blocks, window,
+                nat.ORDER_COL_CAP, rows_per_wg, n_xcd, chunks, 0, out.data_ptr()),
+                "hgd_col_block_order_greedy")
+        else:
+            nat.check(lib.hgd_row_order_greedy(
+                rowptr.data_ptr(), cp, self.n_rows, self.n_cols, window, nat.ORDER_COL_CAP,
+                rows_per_wg, n_xcd, chunks, 0, out.data_ptr()), "hgd_row_order_greedy")
+        return out.to(self.device)
+
+    def col_blocks_ordered(self, n_blocks: int, kind: int = nat.ORDER_MIN_COLUMN,
+                           geom: Optional[tuple] = None) -> Tuple[torch.Tensor, ...]:
         """:meth:`col_blocks` with the rows of every source block in ascending order of their
         first column in that block, for hgd_spmm_blocked_ordered (hgd_spmm_col_blocks_ordered):
         ``(blk_start [n_blocks·n_rows+1] int64, blk_col [nnz] int32, blk_perm [nnz] int32,
         blk_out_row [n_blocks·n_rows] int32)`` — position p of block k holds row
-        ``blk_out_row[k·n_rows + p]``. Built once per block count on the current stream."""
+        ``blk_out_row[k·n_rows + p]``. Built once per block count on the current stream.
+
+        ``kind=ORDER_GREEDY``: every block in the greedy shared-column order for the hop whose
+        ``geom`` is :func:`order_geometry` ``(d, True)``, which is then required
+        (hgd_col_block_order_greedy on the host, then hgd_spmm_col_blocks_ordered_from): built
+        once per block count and geometry, with a stream synchronisation."""
+        if kind == nat.ORDER_GREEDY:
+            return self._col_blocks_greedy(n_blocks, _need_geom(geom))
         got = self._col_blocks_ord.get(n_blocks)
         if got is None:
             if not self.cols_ascending:
@@ -284,26 +357,64 @@ class CSR:
             got = self._col_blocks_ord[n_blocks] = (start, bcol, perm, out_row)
         return got
 
-    def blocked_ordered_values(self, n_blocks: int,
-                               val: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        """``val`` (per-nonzero weights) in the entry order of :meth:`col_blocks_ordered`; cached
-        like :meth:`blocked_values`."""
+    def _col_blocks_greedy(self, n_blocks: int, geom: tuple) -> Tuple[torch.Tensor, ...]:
+        got = self._greedy.get((n_blocks,) + geom)
+        if got is None:
+            if not self.cols_ascending:
+                raise RuntimeError(
+                    "col_blocks_ordered: the rows' columns are not known to be ascending")
+            dev = self.device
+            lib = nat.load()
+            start = torch.empty(n_blocks * self.n_rows + 1, dtype=torch.int64, device=dev)
+            bcol = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+            perm = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+            out_row = self._greedy_order(n_blocks, geom)
+            if self.n_rows:
+                ws = _ws(lib.hgd_spmm_col_blocks_ordered_from_workspace_size(self.n_rows,
+                                                                             n_blocks), dev)
+                nat.check(lib.hgd_spmm_col_blocks_ordered_from(
+                    out_row.data_ptr(), self.rowptr.data_ptr(),
+                    self.col.data_ptr() if self.nnz else None, self.n_rows, self.n_cols, n_blocks,
+                    start.data_ptr(), bcol.data_ptr() if self.nnz else None,
+                    perm.data_ptr() if self.nnz else None, ws.data_ptr(), ws.numel(),
+                    _stream(dev)), "hgd_spmm_col_blocks_ordered_from")
+            else:
+                start.zero_()
+            got = self._greedy[(n_blocks,) + geom] = (start, bcol, perm, out_row)
+        return got
+
+    @staticmethod
+    def _order_key(base, geom: Optional[tuple]):
+        """The cache key of what is gathered through an order: ``base`` for the min-column order
+        (``geom`` None), with the geometry beside it for a greedy one."""
+        return base if geom is None else (base,) + tuple(geom)
+
+    def _blocks_of(self, n_blocks: int, geom: Optional[tuple]):
+        return (self.col_blocks_ordered(n_blocks) if geom is None
+                else self._col_blocks_greedy(n_blocks, geom))
+
+    def blocked_ordered_values(self, n_blocks: int, val: Optional[torch.Tensor],
+                               geom: Optional[tuple] = None) -> Optional[torch.Tensor]:
+        """``val`` (per-nonzero weights) in the entry order of :meth:`col_blocks_ordered` (with
+        ``geom``: of the greedy order of that geometry); cached like :meth:`blocked_values`."""
         if val is None:
             return None
-        return _gather32_cached(self._blk_ord_vals, 2 * n_blocks, val,
-                                self.col_blocks_ordered(n_blocks)[2])
+        return _gather32_cached(self._blk_ord_vals, self._order_key(2 * n_blocks, geom), val,
+                                self._blocks_of(n_blocks, geom)[2])
 
-    def blocked_ordered_scale(self, n_blocks: int,
-                              row_scale: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    def blocked_ordered_scale(self, n_blocks: int, row_scale: Optional[torch.Tensor],
+                              geom: Optional[tuple] = None) -> Optional[torch.Tensor]:
         """``row_scale`` (one per row) as ``[n_blocks·n_rows]`` in the processing order of
-        :meth:`col_blocks_ordered`; cached like :meth:`blocked_values`."""
+        :meth:`col_blocks_ordered` (with ``geom``: of the greedy order of that geometry); cached
+        like :meth:`blocked_values`."""
         if row_scale is None:
             return None
-        return _gather32_cached(self._blk_ord_vals, 2 * n_blocks + 1, row_scale,
-                                self.col_blocks_ordered(n_blocks)[3])
+        return _gather32_cached(self._blk_ord_vals, self._order_key(2 * n_blocks + 1, geom),
+                                row_scale, self._blocks_of(n_blocks, geom)[3])
 
     def packed_entries(self, n_blocks: int, src_scale: torch.Tensor,
-                       idx_bits: int = nat.PACKED_IDX_BITS) -> Optional[tuple]:
+                       idx_bits: int = nat.PACKED_IDX_BITS,
+                       geom: Optional[tuple] = None) -> Optional[tuple]:
         """The entries of :meth:`col_blocks_ordered` packed for hgd_spmm_blocked_packed, for
         per-nonzero weights that are ``src_scale[col]`` (a float32 scale over this structure's
         ``n_cols`` source rows): ``(ent [nnz] int32 bits, dict [n_dict] float32, n_dict)`` with
@@ -318,7 +429,7 @@ class CSR:
             version = src_scale._version
         except RuntimeError:  # an inference tensor tracks no version: built every call
             version = None
-        key = (n_blocks, idx_bits, id(src_scale))
+        key = (self._order_key(n_blocks, geom), idx_bits, id(src_scale))
         hit = self._packed.get(key)
         if (hit is not None and version is not None and hit[0]() is src_scale
                 and hit[1] == version):
@@ -330,7 +441,7 @@ class CSR:
         n_dict = int(bits.numel())
         got = None
         if lib.hgd_spmm_packed_fits(self.n_cols, n_blocks, n_dict, idx_bits):
-            start, bcol, _, _ = self.col_blocks_ordered(n_blocks)
+            start, bcol, _, _ = self._blocks_of(n_blocks, geom)
             code = code.to(torch.int32)
             ent = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
             nat.check(lib.hgd_spmm_pack_entries(
@@ -343,12 +454,20 @@ class CSR:
         self._packed[key] = (weakref.ref(src_scale), version, got)
         return got
 
-    def row_order(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    def row_order(self, kind: int = nat.ORDER_MIN_COLUMN, geom: Optional[tuple] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """The rows in ascending order of their smallest column, for the ordered hop
         (hgd_spmm_row_order): ``(order [n_rows] int32, rowptr_o [n_rows+1] int64, col_o [nnz]
         int32, perm [nnz] int32)`` — position p processes row ``order[p]``, whose nonzeros are
         ``[rowptr_o[p], rowptr_o[p+1])`` of ``col_o`` in their own order; ``perm`` is the source
-        position of every entry. Built once, on the current stream."""
+        position of every entry. Built once, on the current stream.
+
+        ``kind=ORDER_GREEDY``: the greedy shared-column order for the hop whose ``geom`` is
+        :func:`order_geometry` ``(d, False)``, which is then required (hgd_row_order_greedy on the
+        host, then hgd_spmm_row_order_from): built once per geometry, with a stream
+        synchronisation."""
+        if kind == nat.ORDER_GREEDY:
+            return self._row_order_greedy(_need_geom(geom))
         got = self._row_order
         if got is None:
             dev = self.device
@@ -369,19 +488,48 @@ class CSR:
             got = self._row_order = (order, rowptr_o, col_o, perm)
         return got
 
-    def ordered_values(self, val: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        """``val`` (per-nonzero weights) in the entry order of :meth:`row_order`; cached like
-        :meth:`blocked_values`."""
+    def _row_order_greedy(self, geom: tuple) -> Tuple[torch.Tensor, ...]:
+        got = self._greedy.get((0,) + geom)
+        if got is None:
+            dev = self.device
+            lib = nat.load()
+            rowptr_o = torch.empty(self.n_rows + 1, dtype=torch.int64, device=dev)
+            col_o = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+            perm = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+            order = self._greedy_order(0, geom)
+            if self.n_rows:
+                ws = _ws(lib.hgd_spmm_row_order_from_workspace_size(self.n_rows), dev)
+                nat.check(lib.hgd_spmm_row_order_from(
+                    order.data_ptr(), self.rowptr.data_ptr(),
+                    self.col.data_ptr() if self.nnz else None, self.n_rows, self.n_cols,
+                    rowptr_o.data_ptr(), col_o.data_ptr() if self.nnz else None,
+                    perm.data_ptr() if self.nnz else None, ws.data_ptr(), ws.numel(),
+                    _stream(dev)), "hgd_spmm_row_order_from")
+            else:
+                rowptr_o.zero_()
+            got = self._greedy[(0,) + geom] = (order, rowptr_o, col_o, perm)
+        return got
+
+    def _rows_of(self, geom: Optional[tuple]):
+        return self.row_order() if geom is None else self._row_order_greedy(geom)
+
+    def ordered_values(self, val: Optional[torch.Tensor],
+                       geom: Optional[tuple] = None) -> Optional[torch.Tensor]:
+        """``val`` (per-nonzero weights) in the entry order of :meth:`row_order` (with ``geom``:
+        of the greedy order of that geometry); cached like :meth:`blocked_values`."""
         if val is None:
             return None
-        return _gather32_cached(self._ord_vals, 0, val, self.row_order()[3])
+        return _gather32_cached(self._ord_vals, self._order_key(0, geom), val,
+                                self._rows_of(geom)[3])
 
-    def ordered_scale(self, row_scale: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        """``row_scale`` (one per row) in the processing order of :meth:`row_order`; cached
-        like :meth:`blocked_values`."""
+    def ordered_scale(self, row_scale: Optional[torch.Tensor],
+                      geom: Optional[tuple] = None) -> Optional[torch.Tensor]:
+        """``row_scale`` (one per row) in the processing order of :meth:`row_order` (with
+        ``geom``: of the greedy order of that geometry); cached like :meth:`blocked_values`."""
         if row_scale is None:
             return None
-        return _gather32_cached(self._ord_vals, 1, row_scale, self.row_order()[0])
+        return _gather32_cached(self._ord_vals, self._order_key(1, geom), row_scale,
+                                self._rows_of(geom)[0])
 
     @property
     def n_heavy(self) -> int:
@@ -467,12 +615,14 @@ def spmm_blocks_split(csr: CSR, d: int, x_dtype: torch.dtype = torch.float32) ->
 
 
 def spmm_row_order(csr: CSR, d: int) -> bool:
-    """Whether the plain fp32 hop over ``csr`` at width ``d`` walks its rows in ascending order
-    of their smallest column (hgd_spmm_ordered over :meth:`CSR.row_order`).
+    """Whether the plain fp32 hop over ``csr`` at width ``d`` walks its rows in an order of its
+    own (hgd_spmm_ordered over :meth:`CSR.row_order`): ascending smallest column, or the greedy
+    shared-column order — which of the two is :func:`spmm_order_kind`'s answer.
 
     A short row's gathers are spread over the whole source table, so an XCD's 4 MiB of L2 sees
     almost no reuse; rows that share their smallest column processed next to each other make
-    the first gather of most rows an L2 hit. Nothing inside a row changes: the sums are bitwise
+    the first gather of most rows an L2 hit (the greedy order: a fifth of all gathers). Nothing
+    inside a row changes: the sums are bitwise
     those of hgd_spmm. The price is Y rows written in permuted order and one 4-byte row id per
     row. The size rule is the library's (hgd_spmm_row_order_for).
 
@@ -495,8 +645,9 @@ def spmm_row_order(csr: CSR, d: int) -> bool:
 
 def spmm_block_order(csr: CSR, d: int, blocks: int) -> bool:
     """Whether the fp32 source-blocked hop over ``csr`` at width ``d`` in ``blocks`` blocks
-    walks each block's rows in ascending order of their first column in that block
-    (hgd_spmm_blocked_ordered over :meth:`CSR.col_blocks_ordered`).
+    walks each block's rows in an order of the block's own (hgd_spmm_blocked_ordered over
+    :meth:`CSR.col_blocks_ordered`): ascending first column in that block, or the block's greedy
+    shared-column order — which of the two is :func:`spmm_order_kind`'s answer.
 
     :func:`spmm_row_order`'s idea inside one source block: a row piece of ~25 nonzeros gathers
     from the whole slice of the block, so pieces that share their first column processed next to
@@ -518,7 +669,47 @@ def spmm_block_order(csr: CSR, d: int, blocks: int) -> bool:
                                                     int(blocks)))
 
 
-def spmm_packed(csr: CSR, blocks: int, src_scale: Optional[torch.Tensor]) -> Optional[tuple]:
+def spmm_order_kind(csr: CSR, d: int, blocks: int = 0) -> int:
+    """Which order an ordered fp32 hop over ``csr`` at width ``d`` walks (``blocks`` > 1: each
+    source block of the blocked hop), for a hop :func:`spmm_row_order` / :func:`spmm_block_order`
+    has turned on: ``ORDER_MIN_COLUMN`` or ``ORDER_GREEDY``.
+
+    The greedy order picks the next row by how many of its columns the XCD's L2 still holds, and
+    gives every XCD a contiguous part of the rows (hgd_row_order_greedy); it is
+    built on the host from a copy of the structure, once, with a stream synchronisation. Y is
+    bitwise the same under either. The rule is the library's (hgd_spmm_row_order_kind_for):
+    greedy wherever the size rules order the hop; a hop ordered only because the environment
+    forces it walks the min-column order, whose build stays on the stream.
+
+    Only for a structure that persists (``csr.persistent``, set by :meth:`Incidence.persist`: a
+    :class:`ShardedIncidence` says it of its graph). Every other structure — the edge-dropped
+    incidences :meth:`Incidence.drop` makes on every training step, possibly inside a captured
+    step, a learned hypergraph's — walks the min-column order whatever the rule and the
+    environment say: the greedy build copies the structure to the host and synchronises the
+    stream, which a step can neither afford nor, captured, do.
+
+    ``HGD_SPMM_ORDER_KIND``: ``1`` min column, ``2`` greedy wherever a hop is ordered, unset (or
+    ``auto``) = the rule. (``HGD_SPMM_ROW_ORDER`` / ``HGD_SPMM_BLOCK_ORDER`` stay the 0 / 1
+    switches of whether a hop is ordered at all.)"""
+    env = os.environ.get("HGD_SPMM_ORDER_KIND", "")
+    if env not in ("", "auto"):
+        if env not in ("1", "2"):
+            raise ValueError(f"HGD_SPMM_ORDER_KIND must be 1 or 2, got {env!r}")
+    if not getattr(csr, "persistent", False):
+        # made per step (Incidence.drop, a learned hypergraph, ...) or never said to last: the
+        # greedy build — a host copy, seconds of host work, a stream synchronisation that cannot
+        # run inside a capture — would be paid by every step. Not even when the environment
+        # forces it
+        return nat.ORDER_MIN_COLUMN
+    if env not in ("", "auto"):
+        return int(env)
+    kind = nat.load().hgd_spmm_row_order_kind_for(csr.n_rows, csr.n_cols, csr.nnz, int(d),
+                                                  int(blocks))
+    return nat.ORDER_GREEDY if kind == nat.ORDER_GREEDY else nat.ORDER_MIN_COLUMN
+
+
+def spmm_packed(csr: CSR, blocks: int, src_scale: Optional[torch.Tensor],
+                geom: Optional[tuple] = None) -> Optional[tuple]:
     """The packed entries the fp32 block-ordered hop over ``csr`` in ``blocks`` blocks runs on
     (hgd_spmm_blocked_packed over :meth:`CSR.packed_entries`), or ``None`` for the weighted hop.
 
@@ -542,7 +733,7 @@ def spmm_packed(csr: CSR, blocks: int, src_scale: Optional[torch.Tensor]) -> Opt
         return None
     if env != "1" and not rule(csr.n_cols, int(blocks), 1, nat.PACKED_IDX_BITS):
         return None  # (not even with one weight: the scale's are not counted for nothing)
-    got = csr.packed_entries(int(blocks), src_scale)
+    got = csr.packed_entries(int(blocks), src_scale, geom=geom)
     if got is None or env == "1":
         return got
     return got if rule(csr.n_cols, int(blocks), got[2], nat.PACKED_IDX_BITS) else None
@@ -650,14 +841,19 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     sp, n, m, rb, re_ = nat.ptr(row_scale), csr.n_rows, csr.n_cols, int(row_begin), int(row_end)
     xp, ldx, yp, ldy = X.data_ptr(), X.stride(0), out.data_ptr(), out.stride(0)
     wp, st = nat.ptr(ws), _stream(X.device)
-    # the plain fp32 hop over the whole row range may walk its rows in min-column order
+    # the plain fp32 hop over the whole row range may walk its rows in an order of its own
+    # (min column, or greedy shared-column: kind below)
     ordered = (not dt and mask is None and ex is None and not blocks and rb == 0 and re_ == n
                and spmm_row_order(csr, d))
     # and the fp32 source-blocked hop over the whole row range each block's rows in its own
     blk_ordered = (not dt and bool(blocks) and rb == 0 and re_ == n
                    and spmm_block_order(csr, d, blocks))
+    # which order such a hop walks: min column, or the greedy shared-column order
+    kind = spmm_order_kind(csr, d, blocks) if ordered or blk_ordered else nat.ORDER_NONE
+    # (None: the min-column order; the geometry is read once per hop, the orders' cache key)
+    geom = order_geometry(d, bool(blocks)) if kind == nat.ORDER_GREEDY else None
     # ... on packed entries when the weights are a source-row scale with few distinct values
-    packed = spmm_packed(csr, blocks, src_scale) if blk_ordered else None
+    packed = spmm_packed(csr, blocks, src_scale, geom) if blk_ordered else None
     if src_scale is not None:
         if src_scale.dtype != torch.float32 or src_scale.numel() != m:
             raise ValueError(f"{_hop_names(_fused16)[0]}: src_scale must be float32 [n_cols]")
@@ -665,17 +861,18 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
             raise ValueError(f"{_hop_names(_fused16)[0]}: src_scale without val on a hop that "
                              "does not run on packed entries (pass the expanded val beside it)")
     if packed is not None:
-        start, _, _, out_row = csr.col_blocks_ordered(blocks)
+        start, _, _, out_row = csr._blocks_of(blocks, geom)
         ent, wdict, n_dict = packed
         nat.check(lib.hgd_spmm_blocked_packed(
             start.data_ptr(), ent.data_ptr(), wdict.data_ptr(), n_dict, nat.PACKED_IDX_BITS,
-            nat.ptr(csr.blocked_ordered_scale(blocks, row_scale)), out_row.data_ptr(), n, m, xp,
-            ldx, yp, ldy, d, int(epilogue), float(slope), blocks, st), "hgd_spmm_blocked_packed")
+            nat.ptr(csr.blocked_ordered_scale(blocks, row_scale, geom)), out_row.data_ptr(), n,
+            m, xp, ldx, yp, ldy, d, int(epilogue), float(slope), blocks, st),
+            "hgd_spmm_blocked_packed")
     elif ordered:
-        order, rowptr_o, col_o, _ = csr.row_order()
+        order, rowptr_o, col_o, _ = csr._rows_of(geom)
         nat.check(lib.hgd_spmm_ordered(
-            rowptr_o.data_ptr(), col_o.data_ptr(), nat.ptr(csr.ordered_values(val)),
-            nat.ptr(csr.ordered_scale(row_scale)), n, m, rb, re_, xp, ldx, yp, ldy, d,
+            rowptr_o.data_ptr(), col_o.data_ptr(), nat.ptr(csr.ordered_values(val, geom)),
+            nat.ptr(csr.ordered_scale(row_scale, geom)), n, m, rb, re_, xp, ldx, yp, ldy, d,
             int(epilogue), float(slope), plan_ptr, wp, wsb, order.data_ptr(), st),
             "hgd_spmm_ordered")
     elif _fused16:  # (ex: never blocked; a bf16 table: never row-ordered)
@@ -717,11 +914,13 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
             rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, ldx, yp, ldy, d, int(epilogue),
             float(slope), plan_ptr, wp, wsb, st), "hgd_spmm_masked")
     elif blk_ordered:  # (blocks: no mask, no fused epilogue)
-        start, bcol, _, out_row = csr.col_blocks_ordered(blocks)
+        start, bcol, _, out_row = csr._blocks_of(blocks, geom)
         nat.check(lib.hgd_spmm_blocked_ordered(
-            start.data_ptr(), bcol.data_ptr(), nat.ptr(csr.blocked_ordered_values(blocks, val)),
-            nat.ptr(csr.blocked_ordered_scale(blocks, row_scale)), out_row.data_ptr(), n, m, xp,
-            ldx, yp, ldy, d, int(epilogue), float(slope), blocks, st), "hgd_spmm_blocked_ordered")
+            start.data_ptr(), bcol.data_ptr(),
+            nat.ptr(csr.blocked_ordered_values(blocks, val, geom)),
+            nat.ptr(csr.blocked_ordered_scale(blocks, row_scale, geom)), out_row.data_ptr(), n,
+            m, xp, ldx, yp, ldy, d, int(epilogue), float(slope), blocks, st),
+            "hgd_spmm_blocked_ordered")
     elif split_blocks:  # (fp32, no mask, no fused epilogue)
         start, bcol, _ = csr.col_blocks(split_blocks)
         plans = csr.col_block_plans(split_blocks)
@@ -942,6 +1141,14 @@ class Incidence:
         inc = cls(csr, csc, values, val_t)
         inc.perm_t = perm  # CSC position → CSR position (sort-free drop-edge rebuilds)
         return inc
+
+    def persist(self) -> "Incidence":
+        """Says that this structure outlives the steps that hop over it (a dataset's graph, held
+        for a whole run): its hops may then walk the greedy shared-column order, built on the
+        host once with a stream synchronisation (:func:`spmm_order_kind`). Never say it of a
+        structure made per step. Returns ``self``."""
+        self.csr.persistent = self.csc.persistent = True
+        return self
 
     def drop(self, mask: torch.Tensor, keep: float, kept: Optional[int] = None,
              capacity: bool = False) -> "Incidence":

@@ -498,6 +498,9 @@ class ShardedIncidence:
         if transport not in TRANSPORTS:
             raise ValueError(f"ShardedIncidence: transport must be one of {TRANSPORTS}")
         self.inc = inc
+        # the run's graph, hopped over on every step: worth an order built once on the host
+        # (incidence.spmm_order_kind; what Incidence.persist sets)
+        inc.csr.persistent = inc.csc.persistent = True
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.P, self.R = P, R

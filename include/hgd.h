@@ -393,6 +393,73 @@ hgd_status hgd_spmm_blocked_ordered(const int64_t* blk_start, const int32_t* blk
                                     int32_t n_blocks, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The two ordered hops above over ANY row order, and the GREEDY SHARED-COLUMN order they are built
+ * for: the next row walked is one that shares the most columns with what its XCD's L2 still holds
+ * (modelled 20–23 % of a short-row hop's gathers hit L2 against 10 % in min-column
+ * order). The kernels take any order, so Y stays bitwise hgd_spmm's / hgd_spmm_blocked's.
+ *
+ * hgd_row_order_greedy builds the order on the HOST, over host pointers, without a HIP call (the
+ * structure does not change from call to call: once per structure). The rows are cut into n_xcd
+ * natural ranges ("parts"), sized to what each XCD's workgroups hold when workgroup w — positions
+ * [w·rows_per_wg, (w+1)·rows_per_wg), only the last one short — runs on XCD w mod n_xcd; each part
+ * is cut evenly into chunks_per_xcd chunks, every chunk is walked greedily on its own, and
+ * position (n_xcd·s + x)·rows_per_wg + j takes element s·rows_per_wg + j of part x, so XCD x walks
+ * part x from its start to its end. Empty rows come last, in natural order, after the placed ones.
+ *   window:  the gathers an XCD's L2 remembers (hgd_spmm_order_geometry)
+ *   col_cap: a column with more entries in a chunk moves no row (it is in L2 anyway); bounds the
+ *            build at 2·nnz·min(column degree, col_cap) list moves. HGD_ORDER_COL_CAP = 1024
+ *   threads: the chunks run on up to that many std::threads; 0 = min(chunks, OMP_NUM_THREADS if
+ *            set, else 8). The order depends on the other arguments only, never on this one.
+ * hgd_col_block_order_greedy does the same for every source block of a structure whose rows'
+ * columns ascend (hgd_spmm_col_blocks' cuts ⌊n_cols·k / n_blocks⌋): blk_order_out
+ * [n_blocks·n_rows], block k's order at k·n_rows, the rows without a nonzero in the block last.
+ * HGD_ERR_INVALID_ARG for a column outside [0, n_cols) (or columns that do not ascend),
+ * HGD_ERR_WORKSPACE when the host has no memory for a chunk's tables; no exception leaves either.
+ *
+ * hgd_spmm_row_order_from / hgd_spmm_col_blocks_ordered_from are hgd_spmm_row_order /
+ * hgd_spmm_col_blocks_ordered after their sorts, over the caller's DEVICE order (blk_order doubles
+ * as the blk_out_row of the hop): the same outputs for the same order, bit for bit. Both first
+ * check on the device that the order is a permutation (of every block) — a flag array and one
+ * reduction, no atomics — and WAIT FOR THE STREAM to read the answer (the caller copied the
+ * structure to the host to build the order: it has synchronised already; never inside a capture):
+ * HGD_ERR_INVALID_ARG otherwise, before anything is read through the order.
+ *
+ * hgd_spmm_order_geometry: the rows per workgroup and the window of the fp32 hop at width d
+ * (blocked: the source-blocked hop), from the launcher's own pass plan over 16-byte aligned rows;
+ * window = 4 MiB / the bytes of a source row one pass gathers. Returns 0 for a bad argument.
+ * hgd_spmm_row_order_kind_for: the rule both hosts use, HGD_ORDER_* for a hop in n_blocks source
+ * blocks (<= 1: not blocked): HGD_ORDER_GREEDY wherever hgd_spmm_row_order_for /
+ * hgd_spmm_block_order_for order the hop, else HGD_ORDER_NONE.
+ * ---------------------------------------------------------------------------------------- */
+#define HGD_ORDER_NONE 0
+#define HGD_ORDER_MIN_COLUMN 1
+#define HGD_ORDER_GREEDY 2
+#define HGD_ORDER_COL_CAP 1024
+hgd_status hgd_row_order_greedy(const int64_t* rowptr, const int32_t* col, int64_t n_rows,
+                                int64_t n_cols, int64_t window, int32_t col_cap,
+                                int32_t rows_per_wg, int32_t n_xcd, int32_t chunks_per_xcd,
+                                int32_t threads, int32_t* order_out);
+hgd_status hgd_col_block_order_greedy(const int64_t* rowptr, const int32_t* col, int64_t n_rows,
+                                      int64_t n_cols, int32_t n_blocks, int64_t window,
+                                      int32_t col_cap, int32_t rows_per_wg, int32_t n_xcd,
+                                      int32_t chunks_per_xcd, int32_t threads,
+                                      int32_t* blk_order_out);
+size_t hgd_spmm_row_order_from_workspace_size(int64_t n_rows);
+hgd_status hgd_spmm_row_order_from(const int32_t* order, const int64_t* rowptr, const int32_t* col,
+                                   int64_t n_rows, int64_t n_cols, int64_t* rowptr_o,
+                                   int32_t* col_o, int32_t* perm, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+size_t hgd_spmm_col_blocks_ordered_from_workspace_size(int64_t n_rows, int32_t n_blocks);
+hgd_status hgd_spmm_col_blocks_ordered_from(const int32_t* blk_order, const int64_t* rowptr,
+                                            const int32_t* col, int64_t n_rows, int64_t n_cols,
+                                            int32_t n_blocks, int64_t* blk_start, int32_t* blk_col,
+                                            int32_t* blk_perm, void* workspace,
+                                            size_t workspace_bytes, void* stream);
+int32_t hgd_spmm_order_geometry(int32_t d, int32_t blocked, int32_t* rows_per_wg, int64_t* window);
+int32_t hgd_spmm_row_order_kind_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz, int32_t d,
+                                    int32_t n_blocks);
+
+/* ------------------------------------------------------------------------------------------
  * hgd_spmm_blocked_ordered WITHOUT THE WEIGHT STREAM, for weights that are a per-source-row scale
  * expanded over the nonzeros (val[e] = S[col[e]], the degree scales of a binary incidence:
  * torch.sparse.mm(adj.t(), X) with adj = D^-1/2 H ..., model/graph/HGNN_HD4.py:459-462): S has few

@@ -9,13 +9,20 @@ order and a row's gathers in edge order. A gather hits if the same XCD fetched t
 row within its last `window` gathers: at full scale an XCD's 4 MiB of L2 holds 16,384 rows of
 256 B, at --scale 0.1 the window is 1,638; a 512-B row (d = 128) halves it.
 
-It prints the hit share in natural and in min-column order for the hop into users, and for one
-source block of the hop into items (the rows of block 0 of --blocks, in natural order and in
-ascending order of their first column in the block, ties in natural order, empty pieces last).
+It prints the hit share in natural, in min-column and in the greedy shared-column order for the
+hop into users, and for one source block of the hop into items (the rows of block 0 of --blocks,
+in natural order, in ascending order of their first column in the block, ties in natural order,
+empty pieces last, and in the block's greedy order). The greedy order is the library's own
+(hgd_row_order_greedy / hgd_col_block_order_greedy, host code: libhgd.so must be built, no GPU is
+used): placed, every XCD walking its own part cut into --chunks chunks, and for comparison the
+same 8·chunks chunks as one sequence dealt round-robin like any other order.
 
-    python scripts/model_l2_order.py [--scale 0.1 --blocks 4 --window 1638]
+    python scripts/model_l2_order.py [--scale 0.1 --blocks 4 --window 1638 --chunks 1]
 """
 import argparse
+import os
+import sys
+import time
 
 import numpy as np
 
@@ -69,6 +76,41 @@ def min_column_order(rowptr, col, n_cols):
     return np.argsort(key, kind="stable")
 
 
+def _lib():
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from hypergraph_diffusion_for_recommendation_amd import _native as nat
+    return nat
+
+
+def greedy_order(rowptr, col, n_cols, window, chunks=1, placed=True, col_cap=1024, threads=0):
+    """The library's greedy order of the rows: placed on the XCDs (each walks its own part, cut
+    into `chunks` chunks), or the same number of chunks as one unplaced sequence."""
+    nat = _lib()
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    order = np.empty(len(rowptr) - 1, dtype=np.int32)
+    xcds, chunks = (XCDS, chunks) if placed else (1, XCDS * chunks)
+    nat.check(nat.load().hgd_row_order_greedy(
+        rowptr.ctypes.data, col.ctypes.data, len(order), n_cols, window, col_cap, ROWS_PER_WG,
+        xcds, chunks, threads, order.ctypes.data), "hgd_row_order_greedy")
+    return order
+
+
+def greedy_block_orders(rowptr, col, n_cols, n_blocks, window, chunks=1, placed=True,
+                        col_cap=1024, threads=0):
+    """[n_blocks, n_rows]: the library's greedy order of every source block's rows."""
+    nat = _lib()
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    n = len(rowptr) - 1
+    order = np.empty(n_blocks * n, dtype=np.int32)
+    xcds, chunks = (XCDS, chunks) if placed else (1, XCDS * chunks)
+    nat.check(nat.load().hgd_col_block_order_greedy(
+        rowptr.ctypes.data, col.ctypes.data, n, n_cols, n_blocks, window, col_cap, ROWS_PER_WG,
+        xcds, chunks, threads, order.ctypes.data), "hgd_col_block_order_greedy")
+    return order.reshape(n_blocks, n)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--scale", type=float, default=0.1,
@@ -78,6 +120,8 @@ def main():
                     help="gathers an XCD's L2 remembers (default: 16384·scale; halve it for the "
                          "512-B rows of d = 128)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--chunks", type=int, default=1,
+                    help="chunks each XCD's part of the greedy order is cut into")
     args = ap.parse_args()
     U, I, E = (int(round(n * args.scale)) for n in (10_000_000, 1_000_000, 100_000_000))
     window = args.window if args.window is not None else int(16384 * args.scale)
@@ -87,6 +131,13 @@ def main():
     nat = hit_share(rowptr, col, np.arange(U), window)
     ordered = hit_share(rowptr, col, min_column_order(rowptr, col, I), window)
     print(f"into users: natural {100 * nat:.2f} %, min-column order {100 * ordered:.2f} %")
+    t0 = time.perf_counter()
+    placed = greedy_order(rowptr, col, I, window, args.chunks)
+    build_s = time.perf_counter() - t0
+    unplaced = greedy_order(rowptr, col, I, window, args.chunks, placed=False)
+    print(f"into users: greedy order, {args.chunks} chunk(s) per XCD part: placed "
+          f"{100 * hit_share(rowptr, col, placed, window):.2f} %, the same chunks unplaced "
+          f"{100 * hit_share(rowptr, col, unplaced, window):.2f} % (built in {build_s:.2f} s)")
 
     # block 0 of the hop into items: the CSC's entries among the first U/P users
     cptr, crow = transpose(rowptr, col, I)
@@ -99,6 +150,13 @@ def main():
     ordered = hit_share(bptr, bcol, order, window)
     print(f"into items, one of {args.blocks} blocks: natural {100 * nat:.2f} %, "
           f"block min-column order {100 * ordered:.2f} %")
+    # (the library cuts the blocks at ⌊U·k / blocks⌋: block 0 is the same [0, U // blocks))
+    placed = greedy_block_orders(cptr, crow, U, args.blocks, window, args.chunks)[0]
+    unplaced = greedy_block_orders(cptr, crow, U, args.blocks, window, args.chunks,
+                                   placed=False)[0]
+    print(f"into items, one of {args.blocks} blocks: greedy order placed "
+          f"{100 * hit_share(bptr, bcol, placed, window):.2f} %, unplaced "
+          f"{100 * hit_share(bptr, bcol, unplaced, window):.2f} %")
 
 
 if __name__ == "__main__":
