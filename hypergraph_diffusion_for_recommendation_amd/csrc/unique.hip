@@ -279,6 +279,12 @@ __device__ __forceinline__ void uq_emit(const uint32_t* bitmap, const State* st,
 // are all smaller: the output stays torch.unique's sorted order.
 constexpr int kFarThreads = 1024;
 constexpr int kFarLds = 4096;
+// uq_far and block_bitonic count the far keys, their padded power of two P and the bitonic
+// `size` in `int`. Every key but the smallest (the window starts at it) may be a far key, so the
+// device-complete entries take at most 2^29 keys: then P <= 2^29, and block_bitonic's `size`
+// leaves its loop at 2·P <= 2^30 — with P = 2^30 its last `size <<= 1` would overflow and the
+// loop never end, as `P <<= 1` would beyond that. k + t, 2·i and c0 + t stay below 2^30 + 2^10.
+constexpr int64_t kFarMaxKeys = int64_t(1) << 29;
 
 __device__ __forceinline__ void cas(int64_t& a, int64_t& b, bool up) {
   if ((a > b) == up) {
@@ -507,6 +513,7 @@ template <class Src, bool DEV = false>
 hgd_status unique_bitmap(Src src, int64_t n, int64_t* out, int64_t* n_out, void* ws, size_t wsb,
                          hipStream_t st, const char* fn) {
   HGD_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "%s: n must be in [0, 2^31)", fn);
+  HGD_REQUIRE(!DEV || n <= kFarMaxKeys, "%s: n must be in [0, 2^29]", fn);
   HGD_REQUIRE(n_out && (n == 0 || out), "%s: null output", fn);
   const size_t need = DEV ? dev_path_bytes(n) : kBitmapPathBytes;
   if (wsb < need || !ws)
@@ -576,7 +583,7 @@ hgd_status unique_group(const hgd_unique_job* jobs, int count, hipStream_t st, c
   int64_t n_max = 0;
   for (int k = 0; k < count; ++k) {
     const hgd_unique_job& q = jobs[k];
-    HGD_REQUIRE(q.n >= 0 && q.n < (int64_t(1) << 31), "%s: list %d: n must be in [0, 2^31)", fn, k);
+    HGD_REQUIRE(q.n >= 0 && q.n <= kFarMaxKeys, "%s: list %d: n must be in [0, 2^29]", fn, k);
     HGD_REQUIRE(q.n_out && (q.n == 0 || q.out), "%s: list %d: null output", fn, k);
     HGD_REQUIRE(q.n == 0 || (q.x_f32 != nullptr) != (q.x_i64 != nullptr),
                 "%s: list %d: exactly one of x_f32 / x_i64", fn, k);

@@ -1313,7 +1313,8 @@ def unique_long_n(x: torch.Tensor, n_rows: Optional[int] = None
     [-n_rows, n_rows), so no valid list is longer (HCCF's ``torch.unique(anchor_emb.long())``,
     HCCF.py:65-66, reads a [B, d] table of a handful of distinct ints — B·d capacity made every
     InfoNCE buffer and grid that size); a list of out-of-range ids is cut to the capacity, and
-    such ids are the caller's error either way (the reference's gather raises)."""
+    such ids are the caller's error either way (the reference's gather raises). At most 2^29
+    values per tensor (the far-key sort's 32-bit counters; more is refused, include/hgd.h)."""
     return unique_long_n_group([x], [n_rows])[0]
 
 

@@ -1254,7 +1254,10 @@ hgd_status hgd_unique_sort_trunc_f32(const float* x, int64_t n, int64_t* out, in
 /* Device-complete form (a captured training step cannot take the host-side fallback): the
  * bitmap window is [min, min + 2^24); keys beyond it are collected and sorted by one workgroup
  * (in LDS up to 4,096 of them, else a bitonic network over the workspace) and appended — they
- * are all larger. *n_out is always the unique count. Same output as the forms above. */
+ * are all larger. *n_out is always the unique count. Same output as the forms above.
+ * n in [0, 2^29] (HGD_ERR_INVALID_ARG beyond): every key but the smallest may be a far key, and
+ * the far sort counts them, their padded power of two P and the bitonic pass size, which
+ * reaches 2·P, in 32-bit ints. */
 hgd_status hgd_unique_dev_i64(const int64_t* keys, int64_t n, int64_t* out, int64_t* n_out,
                               void* workspace, size_t workspace_bytes, void* stream);
 hgd_status hgd_unique_dev_trunc_f32(const float* x, int64_t n, int64_t* out, int64_t* n_out,
@@ -1266,7 +1269,8 @@ hgd_status hgd_unique_dev_trunc_f32(const float* x, int64_t n, int64_t* out, int
  * (truncated like Tensor.long()) and x_i64, and its own workspace of
  * hgd_unique_workspace_size(n) bytes. `capacity` (0 = n): *n_out is clamped to it and
  * out[*n_out, capacity) zeroed — a fixed-size list whose live count stays on the device (the
- * capacity-sized node lists HCCF's InfoNCE reads). count is 1 to 4. */
+ * capacity-sized node lists HCCF's InfoNCE reads). count is 1 to 4; per list n in [0, 2^29] and
+ * capacity in [0, n] (HGD_ERR_INVALID_ARG otherwise). */
 typedef struct hgd_unique_job {
   const float* x_f32;
   const int64_t* x_i64;
