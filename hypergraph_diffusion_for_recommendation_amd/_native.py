@@ -291,6 +291,10 @@ _SIGNATURES = {
                                      c_i32, c_i32, c_void_p]),
     "hgd_col_block_order_greedy": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_i64, c_i32,
                                            c_i32, c_i32, c_i32, c_i32, c_void_p]),
+    "hgd_row_order_greedy_pooled": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i32, c_i32,
+                                            c_i32, c_i32, c_i32, c_void_p]),
+    "hgd_col_block_order_greedy_pooled": (c_i32, [c_void_p, c_void_p, c_i64, c_i64, c_i32, c_i64,
+                                                  c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p]),
     "hgd_spmm_row_order_from_workspace_size": (c_size, [c_i64]),
     "hgd_spmm_row_order_from": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size, c_void_p]),

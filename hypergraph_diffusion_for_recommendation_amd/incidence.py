@@ -39,6 +39,22 @@ TARGET_GROUPS = 16384
 # the host build)
 ORDER_XCDS = 8
 ORDER_CHUNKS_PER_XCD = 1
+# the XCDs whose walkers pick their rows from one shared pool (hgd_row_order_greedy_pooled; 1: every
+# XCD walks a part of its own; ORDER_XCDS: one pool of all rows, the most L2 hits and the longest
+# build)
+ORDER_XCDS_PER_POOL = 8
+
+
+def order_pool_width() -> int:
+    """The pool width a placed greedy order is built with: ``ORDER_XCDS_PER_POOL``, or what
+    ``HGD_SPMM_ORDER_POOL`` (1, 2, 4 or 8) says. Read when an order is built, once per structure;
+    not part of :func:`order_geometry` or of the key the orders are cached under."""
+    env = os.environ.get("HGD_SPMM_ORDER_POOL", "")
+    if env == "":
+        return ORDER_XCDS_PER_POOL
+    if env not in ("1", "2", "4", "8"):
+        raise ValueError(f"HGD_SPMM_ORDER_POOL must be 1, 2, 4 or 8, got {env!r}")
+    return int(env)
 
 
 def auto_split(n_rows: int, nnz: int) -> Tuple[int, int]:
@@ -301,21 +317,25 @@ class CSR:
         """The greedy order on the device: hgd_row_order_greedy (``n_blocks`` = 0) or
         hgd_col_block_order_greedy over a host copy of ``rowptr`` and ``col``, made for this
         build alone — a stream synchronisation, once per structure and geometry, outside any
-        capture."""
+        capture. A placed geometry (``n_xcd`` > 1) takes the pooled builders, the XCDs sharing
+        pools :func:`order_pool_width` wide."""
         window, rows_per_wg, n_xcd, chunks = geom
+        pool = order_pool_width() if n_xcd > 1 else 0
+        if pool == 1 and chunks != 1:  # (parts cut into chunks: the builder that cuts them)
+            pool = 0
+        if pool and n_xcd % pool:
+            raise ValueError(f"a pool of {pool} XCDs does not divide the geometry's {n_xcd}")
         rowptr, col = self.rowptr.cpu().contiguous(), self.col.cpu().contiguous()
         lib = nat.load()
         out = torch.empty(max(1, n_blocks) * self.n_rows, dtype=torch.int32)
         cp = col.data_ptr() if self.nnz else None
-        if n_blocks:
-            nat.check(lib.hgd_col_block_order_greedy(
-                rowptr.data_ptr(), cp, self.n_rows, self.n_cols, n_blocks, window,
-                nat.ORDER_COL_CAP, rows_per_wg, n_xcd, chunks, 0, out.data_ptr()),
-                "hgd_col_block_order_greedy")
-        else:
-            nat.check(lib.hgd_row_order_greedy(
-                rowptr.data_ptr(), cp, self.n_rows, self.n_cols, window, nat.ORDER_COL_CAP,
-                rows_per_wg, n_xcd, chunks, 0, out.data_ptr()), "hgd_row_order_greedy")
+        name = ("hgd_col_block_order_greedy" if n_blocks else "hgd_row_order_greedy") + \
+            ("_pooled" if pool else "")
+        args = (rowptr.data_ptr(), cp, self.n_rows, self.n_cols) + \
+            ((n_blocks,) if n_blocks else ()) + \
+            (window, nat.ORDER_COL_CAP, rows_per_wg, n_xcd, pool if pool else chunks, 0,
+             out.data_ptr())
+        nat.check(getattr(lib, name)(*args), name)
         return out.to(self.device)
 
     def col_blocks_ordered(self, n_blocks: int, kind: int = nat.ORDER_MIN_COLUMN,

@@ -15,9 +15,11 @@ in natural order, in ascending order of their first column in the block, ties in
 empty pieces last, and in the block's greedy order). The greedy order is the library's own
 (hgd_row_order_greedy / hgd_col_block_order_greedy, host code: libhgd.so must be built, no GPU is
 used): placed, every XCD walking its own part cut into --chunks chunks, and for comparison the
-same 8·chunks chunks as one sequence dealt round-robin like any other order.
+same 8·chunks chunks as one sequence dealt round-robin like any other order. With --pool, beside
+them the pooled greedy orders (hgd_row_order_greedy_pooled / hgd_col_block_order_greedy_pooled):
+the XCDs that many at a time taking their rows in turn from one shared pool.
 
-    python scripts/model_l2_order.py [--scale 0.1 --blocks 4 --window 1638 --chunks 1]
+    python scripts/model_l2_order.py [--scale 0.1 --blocks 4 --window 1638 --chunks 1 --pool 1 8]
 """
 import argparse
 import os
@@ -111,6 +113,32 @@ def greedy_block_orders(rowptr, col, n_cols, n_blocks, window, chunks=1, placed=
     return order.reshape(n_blocks, n)
 
 
+def pooled_order(rowptr, col, n_cols, window, pool, col_cap=1024, threads=0):
+    """The library's pooled greedy order of the rows: the XCDs `pool` at a time take their rows in
+    turn from one shared pool (1: every XCD walks its own part, the placed order above)."""
+    nat = _lib()
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    order = np.empty(len(rowptr) - 1, dtype=np.int32)
+    nat.check(nat.load().hgd_row_order_greedy_pooled(
+        rowptr.ctypes.data, col.ctypes.data, len(order), n_cols, window, col_cap, ROWS_PER_WG,
+        XCDS, pool, threads, order.ctypes.data), "hgd_row_order_greedy_pooled")
+    return order
+
+
+def pooled_block_orders(rowptr, col, n_cols, n_blocks, window, pool, col_cap=1024, threads=0):
+    """[n_blocks, n_rows]: the library's pooled greedy order of every source block's rows."""
+    nat = _lib()
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    n = len(rowptr) - 1
+    order = np.empty(n_blocks * n, dtype=np.int32)
+    nat.check(nat.load().hgd_col_block_order_greedy_pooled(
+        rowptr.ctypes.data, col.ctypes.data, n, n_cols, n_blocks, window, col_cap, ROWS_PER_WG,
+        XCDS, pool, threads, order.ctypes.data), "hgd_col_block_order_greedy_pooled")
+    return order.reshape(n_blocks, n)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--scale", type=float, default=0.1,
@@ -122,6 +150,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--chunks", type=int, default=1,
                     help="chunks each XCD's part of the greedy order is cut into")
+    ap.add_argument("--pool", type=int, nargs="*", choices=[1, 2, 4, 8], default=[],
+                    help="also walk the pooled greedy orders of these widths (XCDs to a shared "
+                         "pool; one chunk per part)")
     args = ap.parse_args()
     U, I, E = (int(round(n * args.scale)) for n in (10_000_000, 1_000_000, 100_000_000))
     window = args.window if args.window is not None else int(16384 * args.scale)
@@ -138,6 +169,13 @@ def main():
     print(f"into users: greedy order, {args.chunks} chunk(s) per XCD part: placed "
           f"{100 * hit_share(rowptr, col, placed, window):.2f} %, the same chunks unplaced "
           f"{100 * hit_share(rowptr, col, unplaced, window):.2f} % (built in {build_s:.2f} s)")
+
+    for pool in args.pool:
+        t0 = time.perf_counter()
+        order = pooled_order(rowptr, col, I, window, pool)
+        build_s = time.perf_counter() - t0
+        print(f"into users: pooled greedy order, {pool} XCD(s) to a pool: "
+              f"{100 * hit_share(rowptr, col, order, window):.2f} % (built in {build_s:.2f} s)")
 
     # block 0 of the hop into items: the CSC's entries among the first U/P users
     cptr, crow = transpose(rowptr, col, I)
@@ -157,6 +195,13 @@ def main():
     print(f"into items, one of {args.blocks} blocks: greedy order placed "
           f"{100 * hit_share(bptr, bcol, placed, window):.2f} %, unplaced "
           f"{100 * hit_share(bptr, bcol, unplaced, window):.2f} %")
+    for pool in args.pool:
+        t0 = time.perf_counter()
+        order = pooled_block_orders(cptr, crow, U, args.blocks, window, pool)[0]
+        build_s = time.perf_counter() - t0
+        print(f"into items, one of {args.blocks} blocks: pooled greedy order, {pool} XCD(s) to a "
+              f"pool: {100 * hit_share(bptr, bcol, order, window):.2f} % (all blocks built in "
+              f"{build_s:.2f} s)")
 
 
 if __name__ == "__main__":
