@@ -339,6 +339,45 @@ _SIGNATURES = {
                                          c_void_p, c_i64, c_i32, ctypes.POINTER(RowEpilogue),
                                          c_void_p, c_i64, ctypes.POINTER(SplitPlan), c_void_p,
                                          c_size, c_void_p]),
+    # the ordered twins: their twin's arguments with out_row before stream
+    "hgd_spmm_fused_ordered": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64,
+                                       c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i32,
+                                       ctypes.POINTER(RowEpilogue), ctypes.POINTER(SplitPlan),
+                                       c_void_p, c_size, c_void_p, c_void_p]),
+    "hgd_spmm_masked_ordered": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_f32, c_void_p,
+                                        c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p,
+                                        c_i64, c_i32, c_i32, c_f32, ctypes.POINTER(SplitPlan),
+                                        c_void_p, c_size, c_void_p, c_void_p]),
+    "hgd_spmm_masked_fused_ordered": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_f32,
+                                              c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p,
+                                              c_i64, c_void_p, c_i64, c_i32,
+                                              ctypes.POINTER(RowEpilogue),
+                                              ctypes.POINTER(SplitPlan), c_void_p, c_size,
+                                              c_void_p, c_void_p]),
+    "hgd_spmm_ordered_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64,
+                                    c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i32, c_i64, c_i32,
+                                    c_i32, c_f32, ctypes.POINTER(SplitPlan), c_void_p, c_size,
+                                    c_void_p, c_void_p]),
+    "hgd_spmm_masked_ordered_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_f32,
+                                           c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i32,
+                                           c_i64, c_void_p, c_i32, c_i64, c_i32, c_i32, c_f32,
+                                           ctypes.POINTER(SplitPlan), c_void_p, c_size, c_void_p,
+                                           c_void_p]),
+    "hgd_spmm_fused_ordered_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64,
+                                          c_i64, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_i64,
+                                          c_i32, ctypes.POINTER(RowEpilogue), c_void_p, c_i64,
+                                          ctypes.POINTER(SplitPlan), c_void_p, c_size, c_void_p,
+                                          c_void_p]),
+    "hgd_spmm_masked_fused_ordered_dt": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_f32,
+                                                 c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p,
+                                                 c_i32, c_i64, c_void_p, c_i64, c_i32,
+                                                 ctypes.POINTER(RowEpilogue), c_void_p, c_i64,
+                                                 ctypes.POINTER(SplitPlan), c_void_p, c_size,
+                                                 c_void_p, c_void_p]),
+    "hgd_spmm_order_geometry_dt": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32,
+                                           ctypes.POINTER(c_i32), ctypes.POINTER(c_i64)]),
+    "hgd_spmm_row_order_for_dt": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
+                                          c_i32]),
     "hgd_row_epilogue_forward": (c_i32, [c_void_p, c_i64, c_i64, c_i32,
                                          ctypes.POINTER(RowEpilogue), c_void_p, c_i64,
                                          c_void_p]),

@@ -396,22 +396,49 @@ extern "C" hgd_status hgd_spmm_row_order_from(const int32_t* order, const int64_
                         reinterpret_cast<int64_t*>(ws + w.len), ws + w.tail, w.total - w.tail, st);
 }
 
-extern "C" int32_t hgd_spmm_order_geometry(int32_t d, int32_t blocked, int32_t* rows_per_wg,
-                                           int64_t* window) {
-  using namespace hgd;
+namespace hgd {
+namespace {
+
+// The rows per workgroup and the window of the hop of one form (sx / sy: the element sizes of X
+// and Y; fused: with a row epilogue, which has no LayerNorm here: the plan of a row of any
+// width), from the launcher's own pass plan over 16-byte aligned rows of d (a blocked hop: any
+// block count).
+int32_t order_geometry(const char* fn, int32_t d, int32_t blocked, size_t sx, size_t sy,
+                       bool fused, int32_t* rows_per_wg, int64_t* window) {
   if (d <= 0 || !rows_per_wg || !window) return 0;
-  // the fp32 hop's own pass plan over 16-byte aligned rows of d (a blocked hop: any block count)
-  SpmmRequest r{"hgd_spmm_order_geometry", nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0,
+  SpmmRequest r{fn, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0,
                 nullptr, d, nullptr, d, d, HGD_EPI_NONE, 0.f};
   r.blocked = blocked != 0;
   r.n_blk = blocked ? 2 : 0;
+  const hgd_row_epilogue ex{};
+  if (fused) r.ex = &ex;
   SpmmPassPlan p;
-  if (spmm_pass_plan(r, 4, 4, &p) != HGD_OK) return 0;
+  if (spmm_pass_plan(r, sx, sy, &p) != HGD_OK) return 0;
   *rows_per_wg = kBlock / p.G;
   // the gathers an XCD's 4 MiB of L2 holds: one is a pass's piece of a source row
-  const int64_t piece = static_cast<int64_t>(d < p.step ? d : p.step) * 4;
+  const int64_t piece = static_cast<int64_t>(d < p.step ? d : p.step) * static_cast<int64_t>(sx);
   *window = (int64_t(4) << 20) / piece;
   return 1;
+}
+
+}  // namespace
+}  // namespace hgd
+
+extern "C" int32_t hgd_spmm_order_geometry(int32_t d, int32_t blocked, int32_t* rows_per_wg,
+                                           int64_t* window) {
+  return hgd::order_geometry("hgd_spmm_order_geometry", d, blocked, 4, 4, false, rows_per_wg,
+                             window);
+}
+
+extern "C" int32_t hgd_spmm_order_geometry_dt(int32_t d, int32_t blocked, int32_t x_dtype,
+                                              int32_t y_dtype, int32_t fused,
+                                              int32_t* rows_per_wg, int64_t* window) {
+  const bool xb = x_dtype == HGD_DT_BF16, yb = y_dtype == HGD_DT_BF16;
+  if ((!xb && x_dtype != HGD_DT_F32) || (!yb && y_dtype != HGD_DT_F32)) return 0;
+  // no such hop: a fused row epilogue into a 16-bit Y, or over source blocks
+  if (fused && (yb || blocked)) return 0;
+  return hgd::order_geometry("hgd_spmm_order_geometry_dt", d, blocked, xb ? 2 : 4, yb ? 2 : 4,
+                             fused != 0, rows_per_wg, window);
 }
 
 extern "C" int32_t hgd_spmm_row_order_kind_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz,
@@ -434,6 +461,39 @@ extern "C" int32_t hgd_spmm_row_order_for(int64_t n_rows, int64_t n_src_rows, in
   // between the two bounds it is on: at 10 M users × 1 M items × 100 M edges the ordered hop into
   // users is 7–8 % faster at d = 32, 64 and 128 (scripts/bench_row_order.py)
   return 1;
+}
+
+extern "C" int32_t hgd_spmm_row_order_for_dt(int64_t n_rows, int64_t n_src_rows, int64_t nnz,
+                                             int32_t d, int32_t x_dtype, int32_t y_dtype,
+                                             int32_t fused, int32_t masked) {
+  const bool xb = x_dtype == HGD_DT_BF16, yb = y_dtype == HGD_DT_BF16;
+  if ((!xb && x_dtype != HGD_DT_F32) || (!yb && y_dtype != HGD_DT_F32)) return 0;
+  if (!xb && !yb && !fused && !masked)  // the plain fp32 hop: its own rule
+    return hgd_spmm_row_order_for(n_rows, n_src_rows, nnz, d);
+  // The fused, masked and 16-bit forms are ordered only where the ordered twin beat the unordered
+  // call by more than the rounds' ranges, in both orders a host may pick (min column, greedy).
+  // Measured on MI355X over the bench graph's hop into users, 10 M users × 1 M items × 100 M
+  // edges, 5 interleaved rounds of 10 calls, ranges 0.002–0.04 ms
+  // (scripts/bench_ordered_forms.py, profiles/ordered_forms/):
+  //   fused fp32 (LayerNorm + residual), d = 128: 9.09 → 8.89 ms min column (−2.2 %), 9.31 → 8.86
+  //     greedy (−4.8 %); the LocalAwareEncoder at the Amazon-Book shape, fwd + bwd: −0.5 / −0.6 /
+  //     −0.9 % on three repeats. At d = 64 it loses: +2.7 % min column, +1.4 % greedy;
+  //   plain bf16 → bf16 hop, d = 128: 6.51 → 6.20 ms min column (−4.8 %), 6.43 → 6.03 greedy
+  //     (−6.2 %). At d = 64 the greedy order gains 5.7 % and the min-column order 0.7 %, inside
+  //     the ranges: a rule cannot see which of the two its host walks, so it stays off;
+  //   fused bf16: +9.5 / +7.4 % at d = 64, +1.6 % (min column) / −1.3 % (greedy) at d = 128: off;
+  //   every masked form loses 3–13 % with the per-step gather of its mask counted: off.
+  // So: the two forms that won, at the width they won at, inside the plain rule's two bounds
+  // (the table one pass gathers from, in the form's element size, against the aggregate L2; the
+  // average row length). Everything else, unmeasured widths and dtype pairs included, answers 0
+  // and is reachable through HGD_SPMM_ROW_ORDER=1 in the Python host, as the blocked bf16 hop is
+  // through HGD_SPMM_BLOCKS.
+  if (n_rows <= 0 || n_src_rows <= 0 || nnz <= 0 || masked || d != 128) return 0;
+  const bool fused_f32 = fused && !xb && !yb, plain_bf16 = !fused && xb && yb;
+  if (!fused_f32 && !plain_bf16) return 0;
+  const double table = static_cast<double>(n_src_rows) * d * (xb ? 2.0 : 4.0);
+  if (table < 33554432.0) return 0;
+  return nnz > 32 * n_rows ? 0 : 1;
 }
 
 extern "C" int32_t hgd_spmm_block_order_for(int64_t n_rows, int64_t n_src_rows, int64_t nnz,
@@ -857,5 +917,74 @@ extern "C" hgd_status hgd_spmm_masked_fused(const int64_t* rowptr, const int32_t
   r.masked = true;
   r.mask = mask;
   r.keep = keep;
+  return hgd::spmm_launch<float, float>(r);
+}
+
+// The ordered twins of the three entry points above (hgd_spmm_ordered's contract: rowptr / col /
+// val / row_scale the ordered copies, out_row the order, every row): mask is in the ordered entry
+// order, everything epi points to stays indexed by Y row.
+extern "C" hgd_status hgd_spmm_fused_ordered(const int64_t* rowptr, const int32_t* col,
+                                             const float* val, const float* row_scale,
+                                             int64_t n_rows, int64_t n_src_rows,
+                                             int64_t row_begin, int64_t row_end, const float* X,
+                                             int64_t ldx, float* Y, int64_t ldy, int32_t d,
+                                             const hgd_row_epilogue* epi,
+                                             const hgd_split_plan* plan, void* workspace,
+                                             size_t workspace_bytes, const int32_t* out_row,
+                                             void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(epi != nullptr, "hgd_spmm_fused_ordered: null epilogue descriptor");
+  hgd::SpmmRequest r{"hgd_spmm_fused_ordered", rowptr, col, val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, epi->act, epi->slope, plan, workspace,
+                     workspace_bytes, stream};
+  r.ex = epi;
+  r.ordered = true;
+  r.out_row = out_row;
+  return hgd::spmm_launch<float, float>(r);
+}
+
+extern "C" hgd_status hgd_spmm_masked_ordered(const int64_t* rowptr, const int32_t* col,
+                                              const float* val, const uint8_t* mask, float keep,
+                                              const float* row_scale, int64_t n_rows,
+                                              int64_t n_src_rows, int64_t row_begin,
+                                              int64_t row_end, const float* X, int64_t ldx,
+                                              float* Y, int64_t ldy, int32_t d, int32_t epilogue,
+                                              float slope, const hgd_split_plan* plan,
+                                              void* workspace, size_t workspace_bytes,
+                                              const int32_t* out_row, void* stream) {
+  hgd::clear_error();
+  hgd::SpmmRequest r{"hgd_spmm_masked_ordered", rowptr, col, val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, epilogue, slope, plan, workspace,
+                     workspace_bytes, stream};
+  r.masked = true;
+  r.mask = mask;
+  r.keep = keep;
+  r.ordered = true;
+  r.out_row = out_row;
+  return hgd::spmm_launch<float, float>(r);
+}
+
+extern "C" hgd_status hgd_spmm_masked_fused_ordered(const int64_t* rowptr, const int32_t* col,
+                                                    const float* val, const uint8_t* mask,
+                                                    float keep, const float* row_scale,
+                                                    int64_t n_rows, int64_t n_src_rows,
+                                                    int64_t row_begin, int64_t row_end,
+                                                    const float* X, int64_t ldx, float* Y,
+                                                    int64_t ldy, int32_t d,
+                                                    const hgd_row_epilogue* epi,
+                                                    const hgd_split_plan* plan, void* workspace,
+                                                    size_t workspace_bytes,
+                                                    const int32_t* out_row, void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(epi != nullptr, "hgd_spmm_masked_fused_ordered: null epilogue descriptor");
+  hgd::SpmmRequest r{"hgd_spmm_masked_fused_ordered", rowptr, col, val, row_scale, n_rows,
+                     n_src_rows, row_begin, row_end, X, ldx, Y, ldy, d, epi->act, epi->slope,
+                     plan, workspace, workspace_bytes, stream};
+  r.ex = epi;
+  r.masked = true;
+  r.mask = mask;
+  r.keep = keep;
+  r.ordered = true;
+  r.out_row = out_row;
   return hgd::spmm_launch<float, float>(r);
 }

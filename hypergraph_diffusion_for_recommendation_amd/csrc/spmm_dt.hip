@@ -1,6 +1,7 @@
 // The SpMM hop of spmm.hip over 16-bit tables: hgd_spmm_dt / hgd_spmm_masked_dt /
 // hgd_spmm_blocked_dt, and the fused row epilogue over a bfloat16 table: hgd_spmm_fused_dt /
-// hgd_spmm_masked_fused_dt.
+// hgd_spmm_masked_fused_dt; and the ordered twin of each but the blocked one (hgd_spmm_ordered_dt,
+// hgd_spmm_masked_ordered_dt, hgd_spmm_fused_ordered_dt, hgd_spmm_masked_fused_ordered_dt).
 //
 // Replaces the same call sites as hgd_spmm (torch.sparse.mm(adj, X), model/graph/HCCF.py:199;
 // torch.sparse.mm(adj.t(), X), model/graph/HGNN_HD4.py:459-462, HGCN.py:173-175; paths relative
@@ -208,4 +209,125 @@ extern "C" int32_t hgd_spmm_blocks_for_dt(int64_t n_src_rows, int32_t d, int32_t
   // 5.856 / 7.274; d = 256 in 128-column passes: 11.39 / 11.74 / 14.57 — against a round-to-round
   // spread of 0.01–0.03 ms. The hop is reachable through HGD_SPMM_BLOCKS=P in the Python host.
   return 0;
+}
+
+// The ordered twins of hgd_spmm_dt / hgd_spmm_masked_dt / hgd_spmm_fused_dt /
+// hgd_spmm_masked_fused_dt (hgd_spmm_ordered's contract: rowptr / col / val / row_scale the
+// ordered copies, out_row the order, every row; mask in the ordered entry order; what epi points
+// to and y16 indexed by Y row). f32 → f32 forwards to the fp32 ordered twin, as the unordered
+// entry points forward to theirs.
+extern "C" hgd_status hgd_spmm_ordered_dt(const int64_t* rowptr, const int32_t* col,
+                                          const float* val, const float* row_scale,
+                                          int64_t n_rows, int64_t n_src_rows, int64_t row_begin,
+                                          int64_t row_end, const void* X, int32_t x_dtype,
+                                          int64_t ldx, void* Y, int32_t y_dtype, int64_t ldy,
+                                          int32_t d, int32_t epilogue, float slope,
+                                          const hgd_split_plan* plan, void* workspace,
+                                          size_t workspace_bytes, const int32_t* out_row,
+                                          void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(hgd::dtype_ok(x_dtype) && hgd::dtype_ok(y_dtype),
+              "hgd_spmm_ordered_dt: unknown dtype code (x %d, y %d): HGD_DT_F32 or HGD_DT_BF16",
+              x_dtype, y_dtype);
+  if (x_dtype == HGD_DT_F32 && y_dtype == HGD_DT_F32)
+    return hgd_spmm_ordered(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin, row_end,
+                            static_cast<const float*>(X), ldx, static_cast<float*>(Y), ldy, d,
+                            epilogue, slope, plan, workspace, workspace_bytes, out_row, stream);
+  hgd::SpmmRequest r{"hgd_spmm_ordered_dt", rowptr, col, val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, epilogue, slope, plan, workspace,
+                     workspace_bytes, stream};
+  r.ordered = true;
+  r.out_row = out_row;
+  return hgd::spmm_dt_dispatch(r, x_dtype, y_dtype);
+}
+
+extern "C" hgd_status hgd_spmm_masked_ordered_dt(const int64_t* rowptr, const int32_t* col,
+                                                 const float* val, const uint8_t* mask, float keep,
+                                                 const float* row_scale, int64_t n_rows,
+                                                 int64_t n_src_rows, int64_t row_begin,
+                                                 int64_t row_end, const void* X, int32_t x_dtype,
+                                                 int64_t ldx, void* Y, int32_t y_dtype,
+                                                 int64_t ldy, int32_t d, int32_t epilogue,
+                                                 float slope, const hgd_split_plan* plan,
+                                                 void* workspace, size_t workspace_bytes,
+                                                 const int32_t* out_row, void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(hgd::dtype_ok(x_dtype) && hgd::dtype_ok(y_dtype),
+              "hgd_spmm_masked_ordered_dt: unknown dtype code (x %d, y %d): HGD_DT_F32 or "
+              "HGD_DT_BF16", x_dtype, y_dtype);
+  if (x_dtype == HGD_DT_F32 && y_dtype == HGD_DT_F32)
+    return hgd_spmm_masked_ordered(rowptr, col, val, mask, keep, row_scale, n_rows, n_src_rows,
+                                   row_begin, row_end, static_cast<const float*>(X), ldx,
+                                   static_cast<float*>(Y), ldy, d, epilogue, slope, plan,
+                                   workspace, workspace_bytes, out_row, stream);
+  hgd::SpmmRequest r{"hgd_spmm_masked_ordered_dt", rowptr, col, val, row_scale, n_rows,
+                     n_src_rows, row_begin, row_end, X, ldx, Y, ldy, d, epilogue, slope, plan,
+                     workspace, workspace_bytes, stream};
+  r.masked = true;
+  r.mask = mask;
+  r.keep = keep;
+  r.ordered = true;
+  r.out_row = out_row;
+  return hgd::spmm_dt_dispatch(r, x_dtype, y_dtype);
+}
+
+extern "C" hgd_status hgd_spmm_fused_ordered_dt(const int64_t* rowptr, const int32_t* col,
+                                                const float* val, const float* row_scale,
+                                                int64_t n_rows, int64_t n_src_rows,
+                                                int64_t row_begin, int64_t row_end, const void* X,
+                                                int32_t x_dtype, int64_t ldx, float* Y,
+                                                int64_t ldy, int32_t d,
+                                                const hgd_row_epilogue* epi, void* y16,
+                                                int64_t ld_y16, const hgd_split_plan* plan,
+                                                void* workspace, size_t workspace_bytes,
+                                                const int32_t* out_row, void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(hgd::dtype_ok(x_dtype),
+              "hgd_spmm_fused_ordered_dt: unknown dtype code (x %d): HGD_DT_F32 or HGD_DT_BF16",
+              x_dtype);
+  if (x_dtype == HGD_DT_F32) {
+    if (y16)
+      return hgd::fail(HGD_ERR_UNSUPPORTED,
+                       "hgd_spmm_fused_ordered_dt: y16 needs a bfloat16 table (x HGD_DT_F32)");
+    return hgd_spmm_fused_ordered(rowptr, col, val, row_scale, n_rows, n_src_rows, row_begin,
+                                  row_end, static_cast<const float*>(X), ldx, Y, ldy, d, epi,
+                                  plan, workspace, workspace_bytes, out_row, stream);
+  }
+  hgd::SpmmRequest r{"hgd_spmm_fused_ordered_dt", rowptr, col, val, row_scale, n_rows, n_src_rows,
+                     row_begin, row_end, X, ldx, Y, ldy, d, HGD_EPI_NONE, 0.f, plan, workspace,
+                     workspace_bytes, stream};
+  r.ordered = true;
+  r.out_row = out_row;
+  return hgd::spmm_fused_dt(r, epi, y16, ld_y16);
+}
+
+extern "C" hgd_status hgd_spmm_masked_fused_ordered_dt(
+    const int64_t* rowptr, const int32_t* col, const float* val, const uint8_t* mask, float keep,
+    const float* row_scale, int64_t n_rows, int64_t n_src_rows, int64_t row_begin,
+    int64_t row_end, const void* X, int32_t x_dtype, int64_t ldx, float* Y, int64_t ldy,
+    int32_t d, const hgd_row_epilogue* epi, void* y16, int64_t ld_y16,
+    const hgd_split_plan* plan, void* workspace, size_t workspace_bytes, const int32_t* out_row,
+    void* stream) {
+  hgd::clear_error();
+  HGD_REQUIRE(hgd::dtype_ok(x_dtype),
+              "hgd_spmm_masked_fused_ordered_dt: unknown dtype code (x %d): HGD_DT_F32 or "
+              "HGD_DT_BF16", x_dtype);
+  if (x_dtype == HGD_DT_F32) {
+    if (y16)
+      return hgd::fail(HGD_ERR_UNSUPPORTED, "hgd_spmm_masked_fused_ordered_dt: y16 needs a "
+                       "bfloat16 table (x HGD_DT_F32)");
+    return hgd_spmm_masked_fused_ordered(rowptr, col, val, mask, keep, row_scale, n_rows,
+                                         n_src_rows, row_begin, row_end,
+                                         static_cast<const float*>(X), ldx, Y, ldy, d, epi, plan,
+                                         workspace, workspace_bytes, out_row, stream);
+  }
+  hgd::SpmmRequest r{"hgd_spmm_masked_fused_ordered_dt", rowptr, col, val, row_scale, n_rows,
+                     n_src_rows, row_begin, row_end, X, ldx, Y, ldy, d, HGD_EPI_NONE, 0.f, plan,
+                     workspace, workspace_bytes, stream};
+  r.masked = true;
+  r.mask = mask;
+  r.keep = keep;
+  r.ordered = true;
+  r.out_row = out_row;
+  return hgd::spmm_fused_dt(r, epi, y16, ld_y16);
 }

@@ -99,7 +99,9 @@ constexpr int kPolNtGather = 4;  // gathered X rows: non-temporal loads
 constexpr int kPolPrefetch = 8;  // software-pipelined index batches (see gather_sum)
 
 // Scale, epilogue and store of one finished row r (all G lanes of the group call it together);
-// yr is its row of Y (r, or the ordered hop's out_row[r]).
+// yr is its row of Y (r, or the ordered hop's out_row[r]): everything that belongs to the Y row —
+// Y, the epilogue's side arrays (act_out, stats, res1, res2, sum_res, sum_out) and y16 — is
+// indexed by yr; r is the position, which the caller read rowptr / row_scale / mask at.
 // With EX the hgd_row_epilogue runs in registers: the group holds the whole row (single column
 // pass, checked on the host), so the LayerNorm statistics are two group_sum butterflies; over a
 // 16-bit table (hgd_spmm_fused_dt) the fp32 row that goes to Y is also stored rounded to a.y16.
@@ -146,7 +148,7 @@ __device__ __forceinline__ void finish_row(const SpmmArgsT<TX, TY>& a, int64_t r
   }
   if constexpr (EX) {
     const hgd_row_epilogue& e = a.ex;
-    if (e.act_out && col_ok) store_vec<VEC>(e.act_out + r * e.ld_act + coff, acc);
+    if (e.act_out && col_ok) store_vec<VEC>(e.act_out + yr * e.ld_act + coff, acc);
     if (e.layer_norm) {
       float t = 0.f;
       if (col_ok) {
@@ -161,8 +163,8 @@ __device__ __forceinline__ void finish_row(const SpmmArgsT<TX, TY>& a, int64_t r
       }
       const float rstd = 1.f / sqrtf(group_sum<G>(t) / static_cast<float>(a.d) + e.ln_eps);
       if (e.stats && l == 0) {
-        e.stats[2 * r] = mu;
-        e.stats[2 * r + 1] = rstd;
+        e.stats[2 * yr] = mu;
+        e.stats[2 * yr + 1] = rstd;
       }
       if (col_ok) {
 #pragma unroll
@@ -177,29 +179,29 @@ __device__ __forceinline__ void finish_row(const SpmmArgsT<TX, TY>& a, int64_t r
     for (int i = 0; i < VEC; ++i) acc[i] *= e.out_scale;
     if (e.res1 && col_ok) {
       float rv[VEC];
-      load_vec<VEC>(e.res1 + r * e.ld_res1 + coff, rv);
+      load_vec<VEC>(e.res1 + yr * e.ld_res1 + coff, rv);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = fmaf(e.res1_scale, rv[i], acc[i]);
     }
     if (e.res2 && col_ok) {
       float rv[VEC];
-      load_vec<VEC>(e.res2 + r * e.ld_res2 + coff, rv);
+      load_vec<VEC>(e.res2 + yr * e.ld_res2 + coff, rv);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = fmaf(e.res2_scale, rv[i], acc[i]);
     }
   }
   if (col_ok) store_vec<VEC, NT_STORE>(a.Y + yr * a.ldy + coff, acc);
   if constexpr (EX && sizeof(TX) == 2) {
-    if (a.y16 && col_ok) store_vec<VEC>(a.y16 + r * a.ld_y16 + coff, acc);
+    if (a.y16 && col_ok) store_vec<VEC>(a.y16 + yr * a.ld_y16 + coff, acc);
   }
   if constexpr (EX) {
     const hgd_row_epilogue& e = a.ex;
     if (e.sum_out && col_ok) {
       float rv[VEC];
-      load_vec<VEC>(e.sum_res + r * e.ld_sum_res + coff, rv);
+      load_vec<VEC>(e.sum_res + yr * e.ld_sum_res + coff, rv);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) rv[i] = acc[i] + rv[i];
-      store_vec<VEC>(e.sum_out + r * e.ld_sum_out + coff, rv);
+      store_vec<VEC>(e.sum_out + yr * e.ld_sum_out + coff, rv);
     }
   }
 }
@@ -475,7 +477,9 @@ __device__ __forceinline__ void masked_or_plain_sum(const SpmmArgsT<TX, TY>& a, 
 }
 
 // ORD: the ordered hop (a.out_row set), an instantiation of its own so that every other one is
-// the code it was. PK: the ordered hop over packed entries (a.dict set), one more of its own: the
+// the code it was; with EX, MASK and 16-bit TX / TY too (the ordered twins of the fused, masked
+// and _dt entry points): position r indexes the ordered copies (rowptr, col, val, row_scale and
+// mask, whose entries are in the ordered entry order) and finish_row gets the Y row. PK: the ordered hop over packed entries (a.dict set), one more of its own: the
 // dictionary goes to LDS once per workgroup, before any lane leaves.
 template <int G, int VEC, int U, bool HAS_VAL, int POL, bool EX, bool MASK = false,
           class TX = float, class TY = float, bool ORD = false, bool PK = false>

@@ -73,7 +73,9 @@ struct SpmmRequest {
   bool blocked = false;
   const int64_t* blk_start = nullptr;
   int32_t n_blk = 0;
-  // the row order (hgd_spmm_ordered): position p is written to Y row out_row[p]. With blocked
+  // the row order (hgd_spmm_ordered and the ordered twins of the fused, masked and 16-bit entry
+  // points): position p is written to Y row out_row[p], mask is in the ordered entry order and
+  // ex's side tables and y16 stay indexed by Y row. With blocked
   // (hgd_spmm_blocked_ordered) every source block has its own: out_row and row_scale are
   // [n_blk·n_rows], block k's at k·n_rows, in the processing order of its blk_start
   bool ordered = false;
@@ -111,8 +113,16 @@ inline hgd_status check_launch(const char* fn, const char* what) {
 template <bool HAS_VAL, int G, int VEC, int U, int POL, bool EX, class TX, class TY>
 auto pick_kernel(const SpmmArgsT<TX, TY>& a, bool seg) {
   if constexpr (POL == kDefaultPolicy && U == 8) {
-    // masked (edge-dropped view) hop: the row kernel only
-    if (a.mask) return spmm_kernel<G, VEC, U, HAS_VAL, POL, EX, true, TX, TY>;
+    // masked (edge-dropped view) hop: the row kernel only, in a row order or not
+    if (a.mask) {
+      if (a.out_row) return spmm_kernel<G, VEC, U, HAS_VAL, POL, EX, true, TX, TY, true>;
+      return spmm_kernel<G, VEC, U, HAS_VAL, POL, EX, true, TX, TY>;
+    }
+    // the ordered hop with a fused row epilogue and / or a 16-bit side (the plain fp32 one, which
+    // carries the tuning matrix, is further down)
+    if constexpr (EX || !kF32<TX, TY>) {
+      if (a.out_row) return spmm_kernel<G, VEC, U, HAS_VAL, POL, EX, false, TX, TY, true>;
+    }
   }
   if constexpr (G >= 8 && kSegWalk<EX, TX, TY>) {
     if (seg) return spmm_seg_kernel<G, VEC, U, HAS_VAL, POL, EX, TX, TY>;
@@ -286,18 +296,19 @@ inline hgd_status spmm_check_args(const SpmmRequest& r) {
   }
   if (r.out_row) {
     // the ordered hop is the row kernel over every row: a split plan's chunks and fix-up and the
-    // segmented walk index Y by position, a row range is one of positions, and the fused
-    // epilogue's side tables and the blocked hop's passes are indexed by row — unless the blocks
-    // bring their own orders (hgd_spmm_blocked_ordered: blocked and ordered together)
+    // segmented walk index Y by position, a row range is one of positions, and the blocked hop's
+    // passes are indexed by row — unless the blocks bring their own orders
+    // (hgd_spmm_blocked_ordered: blocked and ordered together), which then take neither a mask nor
+    // a fused row epilogue. Without blocks both go with an order: the mask is read at the ordered
+    // entry position and the epilogue's side tables at the Y row (finish_row)
     if (has_split_rows(r.plan) || (r.plan && (r.plan->flags & HGD_PLAN_SEGMENTED)))
       return fail(HGD_ERR_UNSUPPORTED, "%s: no split rows or segmented walk with a row order", fn);
     if (r.blocked && r.ordered) {
       if (r.mask || ex)
         return fail(HGD_ERR_UNSUPPORTED, "%s: no mask or fused row epilogue with a block order",
                     fn);
-    } else if (r.mask || ex || r.blocked) {
-      return fail(HGD_ERR_UNSUPPORTED,
-                  "%s: no mask, fused row epilogue or source blocks with a row order", fn);
+    } else if (r.blocked) {
+      return fail(HGD_ERR_UNSUPPORTED, "%s: no source blocks with a row order", fn);
     }
     if (r.row_begin != 0 || r.row_end != r.n_rows)
       return fail(HGD_ERR_UNSUPPORTED, "%s: a row order covers all rows, got [%lld,%lld) of %lld",

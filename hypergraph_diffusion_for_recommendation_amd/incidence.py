@@ -88,26 +88,39 @@ def _stream(device) -> int:
     return nat.stream_handle(device)
 
 
-_ORDER_GEOM: Dict[Tuple[int, bool], Tuple[int, int, int, int]] = {}
+_ORDER_GEOM: Dict[tuple, Tuple[int, int]] = {}
 
 
-def order_geometry(d: int, blocked: bool) -> Tuple[int, int, int, int]:
-    """``(window, rows_per_wg, n_xcd, chunks_per_xcd)`` of the greedy order for the fp32 hop at
+def order_geometry(d: int, blocked: bool, x_dtype: torch.dtype = torch.float32,
+                   y_dtype: torch.dtype = torch.float32,
+                   fused: bool = False) -> Tuple[int, int, int, int]:
+    """``(window, rows_per_wg, n_xcd, chunks_per_xcd)`` of the greedy order for the hop at
     width ``d`` (``blocked``: the source-blocked hop): the first two from the launcher's own pass
     plan (hgd_spmm_order_geometry: 16 rows a workgroup and 16,384 gathers in an XCD's L2 at
-    d = 64), the key the orders are cached under. ``HGD_SPMM_ORDER_PLACE=0`` builds the same
+    d = 64), the key the orders are cached under. ``x_dtype`` / ``y_dtype`` / ``fused``: the
+    form of the hop when it is not the plain fp32 one (hgd_spmm_order_geometry_dt) — a 16-bit
+    side has 8-column lanes and a 2·d-byte gathered piece, and the fused row epilogue walks a
+    row wider than 128 columns in one pass. ``HGD_SPMM_ORDER_PLACE=0`` builds the same
     chunks as one sequence, not placed on the XCDs (a measurement switch; unset or ``1``:
     placed)."""
     env = os.environ.get("HGD_SPMM_ORDER_PLACE", "")
     if env not in ("", "0", "1"):
         raise ValueError(f"HGD_SPMM_ORDER_PLACE must be 0 or 1, got {env!r}")
-    got = _ORDER_GEOM.get((int(d), bool(blocked)))
+    plain = x_dtype == torch.float32 and y_dtype == torch.float32 and not fused
+    key = (int(d), bool(blocked)) + (() if plain else (x_dtype, y_dtype, bool(fused)))
+    got = _ORDER_GEOM.get(key)
     if got is None:
         rows, window = ctypes.c_int32(0), ctypes.c_int64(0)
-        if not nat.load().hgd_spmm_order_geometry(int(d), int(bool(blocked)), ctypes.byref(rows),
-                                                  ctypes.byref(window)):
+        if plain:
+            ok = nat.load().hgd_spmm_order_geometry(int(d), int(bool(blocked)),
+                                                    ctypes.byref(rows), ctypes.byref(window))
+        else:
+            ok = nat.load().hgd_spmm_order_geometry_dt(
+                int(d), int(bool(blocked)), _HOP_DTYPES[x_dtype], _HOP_DTYPES[y_dtype],
+                int(bool(fused)), ctypes.byref(rows), ctypes.byref(window))
+        if not ok:
             raise ValueError(f"order_geometry: no pass plan at d = {d}")
-        got = _ORDER_GEOM[(int(d), bool(blocked))] = (int(window.value), int(rows.value))
+        got = _ORDER_GEOM[key] = (int(window.value), int(rows.value))
     if env == "0":
         return got + (1, ORDER_XCDS * ORDER_CHUNKS_PER_XCD)
     return got + (ORDER_XCDS, ORDER_CHUNKS_PER_XCD)
@@ -551,6 +564,31 @@ class CSR:
         return _gather32_cached(self._ord_vals, self._order_key(1, geom), row_scale,
                                 self._rows_of(geom)[0])
 
+    def order_source(self) -> "CSR":
+        """The structure whose row orders, ordered weights and ordered scales this one's hops
+        walk: itself, or for an edge-dropped view (:meth:`Incidence.masked`) its parent — a view
+        is made on every step, and what depends on the structure alone is built once per
+        structure, not once per step."""
+        return getattr(self, "_order_parent", None) or self
+
+    def ordered_mask(self, geom: Optional[tuple] = None) -> torch.Tensor:
+        """An edge-dropped view's ``mask`` in the entry order of its :meth:`order_source`'s
+        :meth:`row_order` (with ``geom``: of the greedy order of that geometry): one
+        hgd_gather_u8 through the order's ``perm``, on the current stream, cached on the view
+        per order — the view's own per-step cost of an ordered hop."""
+        cache = self.__dict__.setdefault("_mask_ord", {})
+        key = self._order_key(0, geom)
+        got = cache.get(key)
+        if got is None:
+            perm = self.order_source()._rows_of(geom)[3]
+            got = torch.empty_like(self.mask)
+            if self.nnz:
+                nat.check(nat.load().hgd_gather_u8(
+                    self.mask.data_ptr(), perm.data_ptr(), self.nnz, got.data_ptr(),
+                    _stream(self.device)), "hgd_gather_u8")
+            cache[key] = got
+        return got
+
     @property
     def n_heavy(self) -> int:
         return int(self.plan.n_heavy) if self.plan.threshold > 0 else 0
@@ -634,10 +672,17 @@ def spmm_blocks_split(csr: CSR, d: int, x_dtype: torch.dtype = torch.float32) ->
         csr.n_cols, int(d), csr.nnz, int(csr.plan.n_chunks), int(csr.plan.chunk)))
 
 
-def spmm_row_order(csr: CSR, d: int) -> bool:
-    """Whether the plain fp32 hop over ``csr`` at width ``d`` walks its rows in an order of its
+def spmm_row_order(csr: CSR, d: int, x_dtype: torch.dtype = torch.float32,
+                   y_dtype: torch.dtype = torch.float32, fused: bool = False,
+                   masked: bool = False) -> bool:
+    """Whether the hop over ``csr`` at width ``d`` walks its rows in an order of its
     own (hgd_spmm_ordered over :meth:`CSR.row_order`): ascending smallest column, or the greedy
-    shared-column order — which of the two is :func:`spmm_order_kind`'s answer.
+    shared-column order — which of the two is :func:`spmm_order_kind`'s answer. Without the
+    keyword arguments the question is the plain fp32 hop's; ``x_dtype`` / ``y_dtype`` (a
+    bfloat16 table or output), ``fused`` (a fused row epilogue) and ``masked`` (an edge-dropped
+    view) ask it of the other forms, whose entry points are the ordered twins of their own
+    (hgd_spmm_fused_ordered, hgd_spmm_masked_ordered, hgd_spmm_ordered_dt, ...) and whose rule
+    is hgd_spmm_row_order_for_dt, set per form by measurement.
 
     A short row's gathers are spread over the whole source table, so an XCD's 4 MiB of L2 sees
     almost no reuse; rows that share their smallest column processed next to each other make
@@ -660,7 +705,11 @@ def spmm_row_order(csr: CSR, d: int) -> bool:
         if env not in ("0", "1"):
             raise ValueError(f"HGD_SPMM_ROW_ORDER must be 0 or 1, got {env!r}")
         return env == "1"
-    return bool(nat.load().hgd_spmm_row_order_for(csr.n_rows, csr.n_cols, csr.nnz, int(d)))
+    if x_dtype == torch.float32 and y_dtype == torch.float32 and not fused and not masked:
+        return bool(nat.load().hgd_spmm_row_order_for(csr.n_rows, csr.n_cols, csr.nnz, int(d)))
+    return bool(nat.load().hgd_spmm_row_order_for_dt(
+        csr.n_rows, csr.n_cols, csr.nnz, int(d), _HOP_DTYPES[x_dtype], _HOP_DTYPES[y_dtype],
+        int(bool(fused)), int(bool(masked))))
 
 
 def spmm_block_order(csr: CSR, d: int, blocks: int) -> bool:
@@ -800,6 +849,12 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     :func:`spmm_blocks_split` whether it runs as hgd_spmm_blocked_split; 0 = never (e.g. into
     uncached exchange memory, which the blocked hop would read back P−1 times).
 
+    A hop over all rows that is not source-blocked walks the structure's row order when
+    :func:`spmm_row_order` says so for its form — plain, masked, fused, 16-bit or any of them
+    together (hgd_spmm_ordered and the ordered twins of the other entry points): the same bits in
+    every output. An edge-dropped view takes the order from its parent (:meth:`CSR.order_source`)
+    and adds one byte gather of its mask (:meth:`CSR.ordered_mask`).
+
     ``_fused16`` / ``_out16`` are :func:`spmm_csr_fused_dt`'s, which runs this body after its
     own checks: the one 16-bit hop that takes ``ex``, and its bf16 copy of the result. A
     rejection then speaks in that function's words (:func:`_hop_names`)."""
@@ -861,17 +916,27 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
     sp, n, m, rb, re_ = nat.ptr(row_scale), csr.n_rows, csr.n_cols, int(row_begin), int(row_end)
     xp, ldx, yp, ldy = X.data_ptr(), X.stride(0), out.data_ptr(), out.stride(0)
     wp, st = nat.ptr(ws), _stream(X.device)
-    # the plain fp32 hop over the whole row range may walk its rows in an order of its own
-    # (min column, or greedy shared-column: kind below)
-    ordered = (not dt and mask is None and ex is None and not blocks and rb == 0 and re_ == n
-               and spmm_row_order(csr, d))
+    # a hop over the whole row range that is not source-blocked may walk its rows in an order of
+    # its own (min column, or greedy shared-column: kind below) — the plain fp32 hop by its size
+    # rule, a masked, fused or 16-bit one by the rule of its form
+    if dt or mask is not None or ex is not None:
+        ordered = (not blocks and rb == 0 and re_ == n
+                   and spmm_row_order(csr, d, X.dtype, y_dtype, ex is not None, mask is not None))
+    else:
+        ordered = not blocks and rb == 0 and re_ == n and spmm_row_order(csr, d)
     # and the fp32 source-blocked hop over the whole row range each block's rows in its own
     blk_ordered = (not dt and bool(blocks) and rb == 0 and re_ == n
                    and spmm_block_order(csr, d, blocks))
     # which order such a hop walks: min column, or the greedy shared-column order
     kind = spmm_order_kind(csr, d, blocks) if ordered or blk_ordered else nat.ORDER_NONE
     # (None: the min-column order; the geometry is read once per hop, the orders' cache key)
-    geom = order_geometry(d, bool(blocks)) if kind == nat.ORDER_GREEDY else None
+    if kind != nat.ORDER_GREEDY:
+        geom = None
+    elif ordered and (dt or ex is not None):
+        # of the form that runs: its lanes, its passes, its gathered piece (a mask changes none)
+        geom = order_geometry(d, False, X.dtype, y_dtype, ex is not None)
+    else:
+        geom = order_geometry(d, bool(blocks))
     # ... on packed entries when the weights are a source-row scale with few distinct values
     packed = spmm_packed(csr, blocks, src_scale, geom) if blk_ordered else None
     if src_scale is not None:
@@ -889,13 +954,53 @@ def spmm_csr(csr: CSR, X: torch.Tensor, val: Optional[torch.Tensor] = None,
             m, xp, ldx, yp, ldy, d, int(epilogue), float(slope), blocks, st),
             "hgd_spmm_blocked_packed")
     elif ordered:
-        order, rowptr_o, col_o, _ = csr._rows_of(geom)
-        nat.check(lib.hgd_spmm_ordered(
-            rowptr_o.data_ptr(), col_o.data_ptr(), nat.ptr(csr.ordered_values(val, geom)),
-            nat.ptr(csr.ordered_scale(row_scale, geom)), n, m, rb, re_, xp, ldx, yp, ldy, d,
-            int(epilogue), float(slope), plan_ptr, wp, wsb, order.data_ptr(), st),
-            "hgd_spmm_ordered")
-    elif _fused16:  # (ex: never blocked; a bf16 table: never row-ordered)
+        # the order and the ordered weights / scales are the structure's: an edge-dropped view
+        # takes them from its parent (built once, not once per step) and brings its mask alone
+        src = csr.order_source()
+        order, rowptr_o, col_o, _ = src._rows_of(geom)
+        rp, cp, op = rowptr_o.data_ptr(), col_o.data_ptr(), order.data_ptr()
+        vp, sp = nat.ptr(src.ordered_values(val, geom)), nat.ptr(src.ordered_scale(row_scale, geom))
+        if mask is not None:
+            mp = csr.ordered_mask(geom).data_ptr()
+        if _fused16:
+            y16p, ld16 = nat.ptr(_out16), 0 if _out16 is None else _out16.stride(0)
+            if mask is not None:
+                nat.check(lib.hgd_spmm_masked_fused_ordered_dt(
+                    rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, nat.DT_BF16, ldx, yp, ldy, d,
+                    ctypes.byref(ex), y16p, ld16, plan_ptr, wp, wsb, op, st),
+                    "hgd_spmm_masked_fused_ordered_dt")
+            else:
+                nat.check(lib.hgd_spmm_fused_ordered_dt(
+                    rp, cp, vp, sp, n, m, rb, re_, xp, nat.DT_BF16, ldx, yp, ldy, d,
+                    ctypes.byref(ex), y16p, ld16, plan_ptr, wp, wsb, op, st),
+                    "hgd_spmm_fused_ordered_dt")
+        elif dt and mask is not None:
+            nat.check(lib.hgd_spmm_masked_ordered_dt(
+                rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, _HOP_DTYPES[X.dtype], ldx, yp,
+                _HOP_DTYPES[y_dtype], ldy, d, int(epilogue), float(slope), plan_ptr, wp, wsb, op,
+                st), "hgd_spmm_masked_ordered_dt")
+        elif dt:
+            nat.check(lib.hgd_spmm_ordered_dt(
+                rp, cp, vp, sp, n, m, rb, re_, xp, _HOP_DTYPES[X.dtype], ldx, yp,
+                _HOP_DTYPES[y_dtype], ldy, d, int(epilogue), float(slope), plan_ptr, wp, wsb, op,
+                st), "hgd_spmm_ordered_dt")
+        elif mask is not None and ex is not None:
+            nat.check(lib.hgd_spmm_masked_fused_ordered(
+                rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, ldx, yp, ldy, d, ctypes.byref(ex),
+                plan_ptr, wp, wsb, op, st), "hgd_spmm_masked_fused_ordered")
+        elif mask is not None:
+            nat.check(lib.hgd_spmm_masked_ordered(
+                rp, cp, vp, mp, keep, sp, n, m, rb, re_, xp, ldx, yp, ldy, d, int(epilogue),
+                float(slope), plan_ptr, wp, wsb, op, st), "hgd_spmm_masked_ordered")
+        elif ex is not None:
+            nat.check(lib.hgd_spmm_fused_ordered(
+                rp, cp, vp, sp, n, m, rb, re_, xp, ldx, yp, ldy, d, ctypes.byref(ex), plan_ptr,
+                wp, wsb, op, st), "hgd_spmm_fused_ordered")
+        else:
+            nat.check(lib.hgd_spmm_ordered(
+                rp, cp, vp, sp, n, m, rb, re_, xp, ldx, yp, ldy, d, int(epilogue), float(slope),
+                plan_ptr, wp, wsb, op, st), "hgd_spmm_ordered")
+    elif _fused16:  # (ex: never blocked)
         y16p, ld16 = nat.ptr(_out16), 0 if _out16 is None else _out16.stride(0)
         if mask is not None:
             nat.check(lib.hgd_spmm_masked_fused_dt(
@@ -1000,8 +1105,10 @@ def spmm_csr_fused_dt(csr: CSR, X16: torch.Tensor, ex: nat.RowEpilogue,
     fp32 over exactly widened elements.
 
     ``out16`` (bfloat16 [n_rows, d]) is filled with the rows of Y rounded to nearest even, from
-    the registers Y was stored from: the table a following hop gathers. Never source-blocked and
-    never walked in a row order, like the fp32 fused hop."""
+    the registers Y was stored from: the table a following hop gathers. Never source-blocked,
+    like the fp32 fused hop; over all rows it walks the structure's row order where
+    :func:`spmm_row_order` turns it on for this form (hgd_spmm_fused_ordered_dt /
+    hgd_spmm_masked_fused_ordered_dt: the same bits, ``out`` and ``out16`` rows included)."""
     if X16.dtype != torch.bfloat16:
         raise TypeError(f"spmm_fused_dt: X16 must be bfloat16, got {X16.dtype}")
     if out is not None and out.dtype != torch.float32:
@@ -1267,6 +1374,11 @@ class Incidence:
         csc = copy.copy(self.csc)
         csr.mask, csr.keep = m, float(keep)
         csc.mask, csc.keep = m_t, float(keep)
+        # a view is made on every step: the row orders and what is gathered through them are the
+        # parent's (CSR.order_source), the mask in an order's entry order is the view's own
+        for view, parent in ((csr, self.csr), (csc, self.csc)):
+            view._order_parent = parent.order_source()
+            view._mask_ord = {}
         out = MaskedIncidence(csr, csc, self.val, self.val_t)
         out.parent = self
         return out

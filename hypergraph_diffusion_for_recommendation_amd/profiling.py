@@ -43,7 +43,8 @@ def impl_bytes(nnz: int, rows: int, d: int, has_val: bool, has_scale: bool,
     block starts instead of the rowptr, writes every Y row P times, reads it back P−1 times and
     applies the row scale in every pass. A blocked hop into a 16-bit Y (hgd_spmm_blocked_dt)
     keeps the running partial in an fp32 scratch instead: P−1 writes and P−1 reads of 4-byte
-    rows, then one store of the 2-byte Y row. An ordered hop (hgd_spmm_ordered) also reads the
+    rows, then one store of the 2-byte Y row. An ordered hop (hgd_spmm_ordered and the ordered
+    twins of the fused, masked and 16-bit hops, with their ``x_bytes`` / ``y_bytes``) also reads the
     int32 output row of every row, a blocked hop over per-block row orders
     (hgd_spmm_blocked_ordered, ``block_ordered``) the one of every row in every block. A blocked
     hop over split rows (hgd_spmm_blocked_split, ``split_chunks`` = the chunks of all its blocks'

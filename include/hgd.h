@@ -336,7 +336,8 @@ int32_t hgd_spmm_blocks_for_dt(int64_t n_src_rows, int32_t d, int32_t x_dtype);
  * hgd_spmm_ordered: hgd_spmm's arguments with rowptr / col / val / row_scale the ORDERED copies
  * and out_row = order: position p writes Y row out_row[p]. HGD_ERR_UNSUPPORTED for a plan with
  * split rows or HGD_PLAN_SEGMENTED and for a row range other than [0, n_rows) (and, inside the
- * library, with a mask, a fused row epilogue or source blocks).
+ * library, with source blocks that bring no orders of their own). With a mask, a fused row
+ * epilogue or a 16-bit side: the ordered twins further down (hgd_spmm_fused_ordered, ...).
  * ---------------------------------------------------------------------------------------- */
 /* The size rule both hosts use: 1 when a hop of nnz nonzeros over n_rows rows
  * gathering n_src_rows rows at width d should run ordered, else 0. */
@@ -684,6 +685,106 @@ hgd_status hgd_spmm_masked_fused_dt(const int64_t* rowptr, const int32_t* col, c
                                     const hgd_row_epilogue* epi, void* y16, int64_t ld_y16,
                                     const hgd_split_plan* plan, void* workspace,
                                     size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The ORDERED TWINS of the fused, masked and 16-bit hops: hgd_spmm_ordered's row walk (any order:
+ * hgd_spmm_row_order's, the greedy one through hgd_spmm_row_order_from) for every hop a model
+ * issues. Each takes its twin's arguments plus out_row before stream, where hgd_spmm_ordered has
+ * it, and replaces the call site its twin replaces when the structure's rows are walked in an
+ * order:
+ *   hgd_spmm_fused_ordered            hgd_spmm_fused            LN0(HGCNConv(adj, Xve)) + Xve,
+ *                                     model/layers/EquivSetConv.py:86-107, model/graph/HGNN_HD3.py:705-720
+ *   hgd_spmm_masked_ordered           hgd_spmm_masked           SpAdjDropEdge + torch.sparse.mm,
+ *                                     model/graph/HCCF.py:213-226, :199
+ *   hgd_spmm_masked_fused_ordered     hgd_spmm_masked_fused     HCCF's layer, model/graph/HCCF.py:182-187
+ *   hgd_spmm_ordered_dt               hgd_spmm_dt               torch.sparse.mm(adj, X) over a 16-bit
+ *   hgd_spmm_masked_ordered_dt        hgd_spmm_masked_dt        table or output, model/graph/HCCF.py:199
+ *   hgd_spmm_fused_ordered_dt         hgd_spmm_fused_dt         the fused layers above over a
+ *   hgd_spmm_masked_fused_ordered_dt  hgd_spmm_masked_fused_dt  bfloat16 table
+ * The ordered copies, indexed by POSITION p (as for hgd_spmm_ordered):
+ *   rowptr, col, val: hgd_spmm_row_order's rowptr_o / col_o and the weights gathered through perm;
+ *   row_scale: the per-row scales gathered through the order (hgd_gather32);
+ *   mask: uint8 [nnz] in the ORDERED ENTRY ORDER — this orientation's mask gathered through the
+ *   order's perm (hgd_gather_u8), entry e of the ordered copy beside col[e] and val[e].
+ * Indexed by Y ROW (position p writes row out_row[p] of each): Y, and everything epi points to —
+ * res1, res2, act_out, stats, sum_res, sum_out — and y16: the caller passes the arrays it passes
+ * to the unordered twin, unchanged. ln_gamma / ln_beta are per column.
+ * Nothing inside a row changes — the same fmaf chain over the (kept) entries in edge order, the
+ * row epilogue in the same registers — so every output is BITWISE the unordered twin's.
+ * HGD_ERR_UNSUPPORTED, before any launch: a plan with split rows or HGD_PLAN_SEGMENTED, a row range
+ * other than [0, n_rows), and a LayerNorm row that does not fit one column pass (as the twin).
+ * HGD_ERR_INVALID_ARG for a null out_row (n_rows > 0). The _dt twins forward f32 → f32 to the fp32
+ * ordered twins, as the unordered ones forward to theirs. Only U = 8 with the default cache policy
+ * is instantiated for these forms, as for their twins.
+ *
+ * hgd_spmm_order_geometry_dt / hgd_spmm_row_order_for_dt: hgd_spmm_order_geometry and
+ * hgd_spmm_row_order_for for the form that will run — x_dtype / y_dtype (HGD_DT_*), fused (with a
+ * row epilogue), masked. The geometry is the launcher's own pass plan of that form: a 16-bit side
+ * has 8-column lanes and 128-column passes, the window counts pieces of min(d, pass) elements of
+ * X, and a fused row is one pass of up to 256 columns (fp32: 64 lanes, 4 rows per workgroup at
+ * d = 256). 0 for an unknown dtype code, a fused hop into a 16-bit Y or over source blocks. The
+ * plain fp32 form answers as the queries above. The rule of every other form is set by
+ * measurement: 0 wherever the ordered twin did not beat the unordered call.
+ * ---------------------------------------------------------------------------------------- */
+hgd_status hgd_spmm_fused_ordered(const int64_t* rowptr, const int32_t* col, const float* val,
+                                  const float* row_scale, int64_t n_rows, int64_t n_src_rows,
+                                  int64_t row_begin, int64_t row_end, const float* X, int64_t ldx,
+                                  float* Y, int64_t ldy, int32_t d, const hgd_row_epilogue* epi,
+                                  const hgd_split_plan* plan, void* workspace,
+                                  size_t workspace_bytes, const int32_t* out_row, void* stream);
+hgd_status hgd_spmm_masked_ordered(const int64_t* rowptr, const int32_t* col, const float* val,
+                                   const uint8_t* mask, float keep, const float* row_scale,
+                                   int64_t n_rows, int64_t n_src_rows, int64_t row_begin,
+                                   int64_t row_end, const float* X, int64_t ldx, float* Y,
+                                   int64_t ldy, int32_t d, int32_t epilogue, float slope,
+                                   const hgd_split_plan* plan, void* workspace,
+                                   size_t workspace_bytes, const int32_t* out_row, void* stream);
+hgd_status hgd_spmm_masked_fused_ordered(const int64_t* rowptr, const int32_t* col,
+                                         const float* val, const uint8_t* mask, float keep,
+                                         const float* row_scale, int64_t n_rows,
+                                         int64_t n_src_rows, int64_t row_begin, int64_t row_end,
+                                         const float* X, int64_t ldx, float* Y, int64_t ldy,
+                                         int32_t d, const hgd_row_epilogue* epi,
+                                         const hgd_split_plan* plan, void* workspace,
+                                         size_t workspace_bytes, const int32_t* out_row,
+                                         void* stream);
+hgd_status hgd_spmm_ordered_dt(const int64_t* rowptr, const int32_t* col, const float* val,
+                               const float* row_scale, int64_t n_rows, int64_t n_src_rows,
+                               int64_t row_begin, int64_t row_end, const void* X, int32_t x_dtype,
+                               int64_t ldx, void* Y, int32_t y_dtype, int64_t ldy, int32_t d,
+                               int32_t epilogue, float slope, const hgd_split_plan* plan,
+                               void* workspace, size_t workspace_bytes, const int32_t* out_row,
+                               void* stream);
+hgd_status hgd_spmm_masked_ordered_dt(const int64_t* rowptr, const int32_t* col, const float* val,
+                                      const uint8_t* mask, float keep, const float* row_scale,
+                                      int64_t n_rows, int64_t n_src_rows, int64_t row_begin,
+                                      int64_t row_end, const void* X, int32_t x_dtype, int64_t ldx,
+                                      void* Y, int32_t y_dtype, int64_t ldy, int32_t d,
+                                      int32_t epilogue, float slope, const hgd_split_plan* plan,
+                                      void* workspace, size_t workspace_bytes,
+                                      const int32_t* out_row, void* stream);
+hgd_status hgd_spmm_fused_ordered_dt(const int64_t* rowptr, const int32_t* col, const float* val,
+                                     const float* row_scale, int64_t n_rows, int64_t n_src_rows,
+                                     int64_t row_begin, int64_t row_end, const void* X,
+                                     int32_t x_dtype, int64_t ldx, float* Y, int64_t ldy,
+                                     int32_t d, const hgd_row_epilogue* epi, void* y16,
+                                     int64_t ld_y16, const hgd_split_plan* plan, void* workspace,
+                                     size_t workspace_bytes, const int32_t* out_row, void* stream);
+hgd_status hgd_spmm_masked_fused_ordered_dt(const int64_t* rowptr, const int32_t* col,
+                                            const float* val, const uint8_t* mask, float keep,
+                                            const float* row_scale, int64_t n_rows,
+                                            int64_t n_src_rows, int64_t row_begin,
+                                            int64_t row_end, const void* X, int32_t x_dtype,
+                                            int64_t ldx, float* Y, int64_t ldy, int32_t d,
+                                            const hgd_row_epilogue* epi, void* y16,
+                                            int64_t ld_y16, const hgd_split_plan* plan,
+                                            void* workspace, size_t workspace_bytes,
+                                            const int32_t* out_row, void* stream);
+int32_t hgd_spmm_order_geometry_dt(int32_t d, int32_t blocked, int32_t x_dtype, int32_t y_dtype,
+                                   int32_t fused, int32_t* rows_per_wg, int64_t* window);
+int32_t hgd_spmm_row_order_for_dt(int64_t n_rows, int64_t n_src_rows, int64_t nnz, int32_t d,
+                                  int32_t x_dtype, int32_t y_dtype, int32_t fused,
+                                  int32_t masked);
 
 /* The same row epilogue applied to an existing matrix Z [n_rows, ldz] (z = Z[r], no hop): the
  * LayerNorms that do not follow a hop, e.g. the MLP InputNorm of model/layers/MLP.py:65-71,109-110.
